@@ -6,7 +6,7 @@ Workload (BASELINE.json configs[1], "C2"): the dense arm of MEVI, i.e. what
 against the 8,841,823 x 768 f32 passage-embedding matrix (27.16 GB, resident in
 HBM), exact inner-product top-1000.  One "step" = one full search of all queries.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]                            (N > 1: starts its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]       (N > 1: starts its own N ranks)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     (the driver's launch line)
 
 Plain `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself -- a CHILD
@@ -101,6 +101,23 @@ def gen_queries(nq, device, n_docs):
     gid = torch.from_numpy(planted_ids(nq, n_docs)).to(device)
     g = torch.Generator(device=device).manual_seed(1234)
     return (blk0[gid] + 0.005 * torch.randn((nq, DIM), device=device, generator=g)).contiguous()
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, scores, ids):
+    """--dump-outputs: what the timed path returned in its last step, for comparing two builds output for output --
+    path/scores.npy (f32 [n, k]), path/ids.npy (the int64 ids as f64, exact below 2**53) and path/query_rows.npy (f64 [n]:
+    the query row of each list).  All nq rows when they fit DUMP_BYTES, else a fixed seeded sample of rows (ascending)."""
+    nq, k = scores.shape
+    n = min(nq, (DUMP_BYTES - 4096) // (k * (4 + 8) + 8))      # 4 KB: the three .npy headers
+    rows = np.arange(nq) if n == nq else np.sort(np.random.default_rng(0).permutation(nq)[:n])
+    sel = torch.from_numpy(rows).to(scores.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "scores.npy"), scores[sel].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "ids.npy"), ids[sel].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "query_rows.npy"), rows.astype(np.float64))
 
 
 def cpu_baseline(n_docs, nq_full, target_s=15.0):
@@ -784,7 +801,11 @@ def main():
     ap.add_argument("--chain-limit-s", type=float, default=420.0, help="N > 1: watchdog of the untimed C5 chain leg")
     ap.add_argument("--exact-f32-path", action="store_true",
                     help="search with the f32-MFMA kernel only (no f16 pre-filter); same results")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's top-k lists as DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))          # before any GPU call; the child's rc is ours
@@ -877,6 +898,8 @@ def main():
     # sanity (untimed): every query's planted neighbour must be its rank-1 hit
     top1 = i[:, 0].cpu().numpy()
     planted_ok = float((top1 == planted_ids(nq, n_docs)).mean())
+    if rank == 0 and args.dump_outputs:         # every rank holds the same merged lists
+        dump_outputs(args.dump_outputs, s, i)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3

@@ -126,3 +126,42 @@ def test_bench_line_is_compact_and_keeps_the_certificate_in_config():
     assert m["dense_lists_identical"] is True and m["beams_identical"] is True and m["chain_mrr10_abs_diff"] == 0.0
     assert line["config"]["chain_c4"]["queries_per_s"] > 0
     assert "per_batch" in full["dense_small_batch"] and "per_batch" not in line.get("dense_small_batch", {})
+
+
+def test_bench_dump_outputs_fits_the_budget_and_is_reproducible(tmp_path):
+    """--dump-outputs at the bench's full size (6980 lists of 1000): a seeded sample of query rows under 64 MB, f32 scores
+    and ids as exact f64, the same rows on every run; a small output is written whole."""
+    import torch
+
+    import bench
+
+    rng = np.random.default_rng(7)
+    nq, k = bench.N_QUERIES, bench.TOPK
+    s = torch.from_numpy(rng.standard_normal((nq, k), dtype=np.float32))
+    i = torch.from_numpy(rng.integers(0, bench.N_DOCS, (nq, k)))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), s, i)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["ids.npy", "query_rows.npy", "scores.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        assert open(tmp_path / "a" / f, "rb").read() == open(tmp_path / "b" / f, "rb").read(), f
+    rows = np.load(tmp_path / "a" / "query_rows.npy")
+    sc, ids = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "ids.npy")
+    assert rows.dtype == np.float64 and sc.dtype == np.float32 and ids.dtype == np.float64
+    assert 4096 < len(rows) < nq and (np.diff(rows) > 0).all() and sc.shape == ids.shape == (len(rows), k)
+    r = rows.astype(np.int64)
+    assert np.array_equal(sc, s.numpy()[r]) and np.array_equal(ids.astype(np.int64), i.numpy()[r])
+
+    bench.dump_outputs(str(tmp_path / "small"), s[:50], i[:50])
+    assert np.array_equal(np.load(tmp_path / "small" / "query_rows.npy"), np.arange(50))
+    assert np.array_equal(np.load(tmp_path / "small" / "ids.npy").astype(np.int64), i.numpy()[:50])
+
+
+def test_bench_refuses_zero_timed_steps():
+    """ms_per_step is the time of one timed step, so there must be at least one (checked before anything is imported)."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr

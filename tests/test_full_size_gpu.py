@@ -187,6 +187,37 @@ def test_bench_starts_its_own_ranks_from_the_plain_command():
     assert bad.returncode != 0 and "WORLD_SIZE" in bad.stderr
 
 
+def test_bench_dump_outputs_are_the_exact_lists(cuda, tmp_path):
+    """`bench.py --dump-outputs DIR` at reduced size: the lists of the last timed step are the C oracle's on the same generated
+    corpus and queries, bit for bit; the line reports the steps asked for and ms_per_step is the time of one of them."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from oracle import dense as odense
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nd, nq, steps = 100_000, 300, 3
+    env = dict(os.environ, PYTHONPATH=root, MEVI_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1", "--docs", str(nd),
+                        "--queries", str(nq), "--no-cpu-baseline", "--no-seq2seq-legs", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    assert line["value"] * line["ms_per_step"] / 1e3 == pytest.approx(nq, rel=1e-3)
+    docs = bench.gen_shard(0, nd, cuda, nd).cpu().numpy()
+    query = bench.gen_queries(nq, cuda, nd).cpu().numpy()
+    es, ei = odense.ip_topk_exact(query, docs, bench.TOPK)
+    out = tmp_path / "out"
+    assert np.array_equal(np.load(out / "query_rows.npy"), np.arange(nq))
+    assert np.array_equal(np.load(out / "ids.npy").astype(np.int64), ei)
+    assert np.array_equal(np.load(out / "scores.npy").view(np.uint32), es.view(np.uint32))
+
+
 def test_bench_over_rccl_when_two_gpus_are_visible():
     """The same line over the real `nccl` (RCCL) backend, one rank per GPU -- runs wherever two devices are visible."""
     if torch.cuda.device_count() < 2:

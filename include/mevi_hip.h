@@ -481,6 +481,10 @@ typedef struct mevi_ip_topk_stats {
   int64_t n_i8_queries;
   int64_t n_i8_unproven;
 } mevi_ip_topk_stats;
+/* The tile walk of the large-batch f16 filter (host arithmetic, no device work): the (corpus tile pair, query tile) items that
+ * workgroup label `label` (blockIdx & 7) takes, in ticket order, for n_dpairs x n_qtiles items.  Writes them when both arrays are
+ * non-null; returns how many there are, -1 on bad arguments. */
+int64_t mevi_ip_filter_tile_walk(int64_t n_dpairs, int64_t n_qtiles, int label, int32_t *dpair, int32_t *qtile);
 void mevi_ip_topk_set_growth(double growth);
 void mevi_ip_topk_set_profiling(int enable); /* 1: record HIP events around every filter/compact launch; 2: also count candidates */
 void mevi_ip_topk_get_stats(mevi_ip_topk_stats *out);

@@ -482,8 +482,9 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_kernel(
 
 __global__ __launch_bounds__(256) void init_state_kernel(unsigned long long *buf, unsigned int *count,
                                                         float *tau, unsigned int *failed, long long nq,
-                                                        int S, int k) {
+                                                        int S, int k, unsigned int *tickets, int n_tickets) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_tickets) tickets[i] = 0u;
   const long long total = nq * (long long)k;
   if (i < total) {
     const long long q = i / k;
@@ -1169,15 +1170,38 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
     const float *__restrict__ Qh, int nq, const float *__restrict__ Dh, long long doc_begin, long long doc_end,
     int dimp, const float *__restrict__ tau, unsigned long long *__restrict__ buf,
     unsigned int *__restrict__ count, int S, int k, int cap, unsigned int id_base, int n_qtiles, int n_dpairs,
-    int flush_mask) {
+    int flush_mask, unsigned int *__restrict__ tickets, unsigned int *__restrict__ tickets_next) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int nwg = n_qtiles * n_dpairs;
-  const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int range_base = (xcd < r8) ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;  // as xcd_remap
-  const int range_len = q8 + (xcd < r8 ? 1 : 0);
-  int item = blockIdx.x >> 3;
+  // Ticketed walk (walk_range / sweep_order, mfma_pp.h): label g = blockIdx & 7 owns items [range_base, range_base + range_len)
+  // of the sweep order; its P workgroups take tickets 0 .. 2P-1 statically (their first two tiles), every later one from the
+  // label's counter tickets[g], so the tiles in flight on an XCD stay ~P consecutive items however the workgroups drift.  Every
+  // ticket below range_len is handed out exactly once, whichever workgroup asks: labels that do not match XCDs cost speed only.
+  // The counters alternate between two sets of eight: init_state_kernel zeroes both, and each launch zeroes the set of the next
+  // one (tickets_next) -- stream order puts that before the next launch's first atomic.
+  // Lane 0 of wave 0 (a staging wave at every NI) takes the ticket of the call after next at the start of an epilogue and
+  // publishes it in the next tile's early() through the word behind the stashes (dynamic LDS: no second __shared__ object);
+  // the windows' barriers order that write before the read in next() and that read before the next write.  The returning
+  // atomic is issued in asm: one more vmcnt entry in front of the ring's pieces, so the ring's counted waits only get stricter,
+  // and the ring's own wait in front of early() retires it (h16_tile_stream).  Written in C++, the compiler -- which cannot
+  // see the ring's waits -- drained vmcnt to zero before the use, once per tile.  Every atomic issued is used by an early()
+  // of a tile that runs (`live`: the next tile exists), so its register is never reused while the atomic is in flight.
+  // A ticket taken for a call that never comes is larger than one already found past the range: unused tickets are never
+  // valid ones.
+  const int g8 = blockIdx.x & 7, P = gridDim.x >> 3, j0 = blockIdx.x >> 3;
+  int range_base, range_len;
+  walk_range(n_qtiles * n_dpairs, g8, range_base, range_len);
+  if (j0 == 0 && threadIdx.x == 0) tickets_next[g8] = 0u;
+  unsigned int *const ctr = tickets + g8;
+  const unsigned int one = 1u;
+  auto take_ticket = [&](unsigned int &v) {
+    asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(v) : "v"(ctr), "v"(one) : "memory");
+  };
+  unsigned int *const tk_word = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(lds) + h1_lds_bytes() + 8 * STASH_BYTES_PER_WAVE);
+  int calls = 0;
+  bool live = false;      // the last next() found a tile
   const int t = threadIdx.x;
+  unsigned int tk = 0u;   // lane 0 of wave 0: the ticket of the call after next
+  if (t == 0 && j0 + P < range_len) take_ticket(tk);   // (else the walk ends within the static tickets)
   const int w8 = __builtin_amdgcn_readfirstlane(t >> 6);
   const int grp = w8 >> 2, wm = (w8 >> 1) & 1, wn = w8 & 1;
   const size_t block_bytes = (size_t)256 * dimp * 2;
@@ -1185,10 +1209,12 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
   int head_d = 0, head_q = 0, tail_d = 0, tail_q = 0, n_pend = 0;
 
   auto next = [&](H1Src &s) -> bool {
-    if (item >= range_len) return false;
+    const int item = calls < 2 ? j0 + calls * P : 2 * P + (int)__builtin_amdgcn_readfirstlane(*tk_word);
+    ++calls;
+    live = item < range_len;
+    if (!live) return false;
     int dpair, qtile;
-    supertile_order<4, 8>(range_base + item, n_dpairs, n_qtiles, dpair, qtile);
-    item += per_xcd;
+    sweep_order(range_base + item, n_dpairs, n_qtiles, dpair, qtile);
     if (n_pend == 0) head_d = dpair, head_q = qtile;
     else tail_d = dpair, tail_q = qtile;
     ++n_pend;
@@ -1214,7 +1240,11 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
   auto begin = [&]() {
     load_tq16<NI>(tq, tau, head_q * QT + 16 * NI * wn, nq);
   };
+  auto early = [&]() {
+    if (t == 0) *tk_word = tk;   // (its atomic was issued at the previous epilogue, or at the kernel's start)
+  };
   auto emit = [&](f32x4 (&acc)[4][NI]) {
+    if (live && t == 0) take_ticket(tk);   // for the call after the next one (the next one will come: `live`)
     const int dpair = head_d, qtile = head_q;
     head_d = tail_d, head_q = tail_q;
     --n_pend;
@@ -1228,7 +1258,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
     ++tiles_done;
     emit_tile16<NI>(acc, tq, qb, drow0 + 64 * wm, doc_end, tau, buf, count, S, k, cap, id_base, stash, (tiles_done & flush_mask) == 0);
   };
-  h16_tile_stream<NI>(64, dimp / 32, lds, next, begin, emit, H1BlockedUnits());
+  h16_tile_stream<NI>(64, dimp / 32, lds, next, begin, emit, early, H1BlockedUnits());
   rec_flush(stash, tau, buf, count, S, k, cap);
 }
 
@@ -1840,10 +1870,13 @@ struct SearchState {
   float *tau;               // [nq]
   unsigned int *failed;     // [nq]
   float *tau_s;             // [nq]  the sampled threshold of the pass's last launch (run_pass), kept for its check
+  unsigned int *tickets;    // [2][8]  the ticket counters of ip_filter_h16_kernel, one per label; launch L uses set L & 1 and
+                            //         zeroes set (L + 1) & 1 for the next
 };
+constexpr int TICKET_SLOTS = 2;
 
 static size_t state_bytes(int64_t nq, const TopkGeom &g) {
-  return align_up((size_t)nq * g.S * 8, 256) + 4 * align_up((size_t)nq * 4, 256);
+  return align_up((size_t)nq * g.S * 8, 256) + 4 * align_up((size_t)nq * 4, 256) + align_up((size_t)TICKET_SLOTS * 8 * 4, 256);
 }
 
 static SearchState carve_state(char *&p, int64_t nq, const TopkGeom &g) {
@@ -1858,6 +1891,8 @@ static SearchState carve_state(char *&p, int64_t nq, const TopkGeom &g) {
   p += align_up((size_t)nq * 4, 256);
   st.tau_s = reinterpret_cast<float *>(p);
   p += align_up((size_t)nq * 4, 256);
+  st.tickets = reinterpret_cast<unsigned int *>(p);
+  p += align_up((size_t)TICKET_SLOTS * 8 * 4, 256);
   return st;
 }
 
@@ -1899,8 +1934,9 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
                         const float *qub = nullptr /* ... and the queries' G_q */) {
   const long long total = nq * (long long)g.k;
   const long long init_n = total > nq ? total : nq;
-  hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((init_n + 255) / 256)), dim3(256), 0, stream,
-                     st.buf, st.count, st.tau, st.failed, (long long)nq, g.S, g.k);
+  const int n_tickets = TICKET_SLOTS * 8;
+  hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)(((init_n > n_tickets ? init_n : n_tickets) + 255) / 256)), dim3(256), 0, stream,
+                     st.buf, st.count, st.tau, st.failed, (long long)nq, g.S, g.k, st.tickets, n_tickets);
   const size_t compact_lds = (size_t)g.S * 8 + 2048;  // keys + histogram
   if (compact_lds > 65536) {  // dynamic LDS beyond 64 KiB must be opted into
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(compact_kernel),
@@ -1965,7 +2001,7 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
     const int64_t v = atoll(e) / (2 * BM) * (2 * BM);
     if (v >= 2 * BM && v < cap_docs) cap_docs = v;
   }
-  size_t pp_lds = h1 ? h1_lds_bytes() + 8 * STASH_BYTES_PER_WAVE : pp_lds_bytes<2>();
+  size_t pp_lds = h1 ? h1_lds_bytes() + 8 * STASH_BYTES_PER_WAVE + 16 /* ip_filter_h16_kernel's ticket word */ : pp_lds_bytes<2>();
   const bool ktail = (dim % BK) != 0;
   const void *fn = nullptr;
 #define MEVI_PICK(NI_, T_) fn = reinterpret_cast<const void *>(ip_filter_kernel<NI_, T_>)
@@ -2073,8 +2109,11 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
         while (T > 1 && T * r > 56.0) T >>= 1;
         flush_mask = T - 1;
       }
+      // this launch's eight ticket counters (zero: init_state_kernel, or the launch before) and the next launch's, which it zeroes
+      unsigned int *tickets = st.tickets + 8 * (launches & 1), *tickets_next = st.tickets + 8 * ((launches + 1) & 1);
       void *args16[] = {(void *)&Q, &nq_i, (void *)&D, &d0, &d1, &dim, (void *)&tau_c, (void *)&st.buf,
-                        (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, &id_base, &n_qt, &n_dp, &flush_mask};
+                        (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, &id_base, &n_qt, &n_dp, &flush_mask,
+                        (void *)&tickets, (void *)&tickets_next};
       void *args_small[] = {(void *)&Q, &nq_i, (void *)&D, &d0, &d1, &dim, (void *)&tau_c, (void *)&st.buf,
                             (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, &id_base, (void *)&row_scale, (void *)&qub};
       if (small) {  // one workgroup per CU, each walking 256-row blocks of the chunk
@@ -2129,6 +2168,19 @@ extern "C" size_t mevi_ip_topk_workspace_bytes(int64_t nq, int64_t dim, int64_t 
   const TopkGeom g = make_geom((int)k);
   // main state + fallback state + gathered fallback queries + index list
   return 2 * state_bytes(nq, g) + align_up((size_t)nq * dim * 4, 256) + align_up((size_t)nq * 4, 256) + 256;
+}
+
+extern "C" int64_t mevi_ip_filter_tile_walk(int64_t n_dpairs, int64_t n_qtiles, int label, int32_t *dpair, int32_t *qtile) {
+  if (n_dpairs <= 0 || n_qtiles <= 0 || n_dpairs * n_qtiles > 0x7fffffffLL || label < 0 || label > 7) return -1;
+  int base, len;
+  walk_range((int)(n_dpairs * n_qtiles), label, base, len);
+  for (int t = 0; t < len && dpair && qtile; ++t) {
+    int a, b;
+    sweep_order(base + t, (int)n_dpairs, (int)n_qtiles, a, b);
+    dpair[t] = a;
+    qtile[t] = b;
+  }
+  return len;
 }
 
 extern "C" void mevi_ip_topk_set_growth(double growth) { g_growth = growth; }

@@ -69,6 +69,31 @@ __device__ inline void supertile_order(int wg, int n_a, int n_b, int &a_tile, in
   b_tile = g * SQ + (r2 - d_in * sq);
 }
 
+// Ticketed walk of the persistent f16 filter (ip_filter_h16_kernel).  One order of all n_a x n_b items: the n_b B-tiles form
+// ceil(n_b / 8) columns of near-equal width w (28 -> 4 x 7); a column sweeps the n_a A-tiles (serpentine: odd columns backwards,
+// so a turn re-uses the A-tiles just fetched), w B-tiles per A-tile.  Label g = blockIdx & 7 owns the g-th of eight contiguous,
+// item-balanced pieces of that order (walk_range) and its workgroups take the items in ticket order from one counter, so the
+// ~32 tiles in flight on an XCD are always ~32 consecutive items: they touch ~32 / w + 1 A-tiles and the column's w B-tiles
+// (12-13 slabs of each 32-k unit at w = 7 or 8), and the column's B-tiles, re-read every w items, stay in L2 while the sweep
+// streams A.  Bijective for any shape; host and device share these functions (mevi_ip_filter_tile_walk exposes them to the
+// tests, tests/test_tile_order_cpu.py).
+__host__ __device__ inline void walk_range(int n_items, int g, int &lo, int &len) {
+  const int q = n_items >> 3, r = n_items & 7;
+  lo = (g < r) ? g * (q + 1) : r * (q + 1) + (g - r) * q;
+  len = q + (g < r ? 1 : 0);
+}
+__host__ __device__ inline void sweep_order(int t, int n_a, int n_b, int &a_tile, int &b_tile) {
+  const int nc = (n_b + 7) >> 3;
+  const int w0 = n_b / nc, wide = n_b - w0 * nc;  // the first `wide` columns are w0 + 1 wide
+  const int c = t / n_a;                           // B-tile index of the column-major walk (columns start at multiples of n_a)
+  const int col = c < wide * (w0 + 1) ? c / (w0 + 1) : wide + (c - wide * (w0 + 1)) / w0;
+  const int b0 = col * w0 + (col < wide ? col : wide), w = w0 + (col < wide ? 1 : 0);
+  const int r = t - b0 * n_a;
+  const int a_in = r / w;
+  a_tile = (col & 1) ? n_a - 1 - a_in : a_in;
+  b_tile = b0 + (r - a_in * w);
+}
+
 // aptr[i]: this thread's staging pointers into its group's A tile (row srow+32i, + skq),
 // bptr[i]: into the shared B tile (row (QT/2)*grp + srow + 32i, + skq); rows pre-clamped.
 // acc[mi][ni]: 32x32 accumulators of wave (wm, wn): A rows 64*wm + 32*mi + ..., B rows

@@ -50,9 +50,12 @@ __device__ __forceinline__ int h16_swz(int quad) { return (quad & 2) ? 3 : 0; }
 //   window g:  ds_read A[g & 1], B[g & 1] <- unit g (4 + NI reads) | 4 NI MFMA  A[(g-1) & 1] x B[(g-1) & 1] | 4 DMA pieces of unit g+3
 // Of the query-side waves only those whose 64 rows exist in the tile stage anything.  An accumulator sums its 32-k products in
 // the same order from a zero-C first product, so the raw scores -- the keys -- are the 256-query tile's, bit for bit.
-template <int NI = 8, class Next, class Begin, class Emit, class UOff = H1PlainUnits, int ABL = 0>
+// early() is called once per tile right after window DEPTH - 2 (window 1 / 2 / 3 at NI = 8 / 4 / 2): the first window whose
+// counted wait (vmcnt(4 (DEPTH - 1)): a staging wave adds four entries per window) has retired every vector-memory instruction
+// the wave issued before the tile's window 0 -- a value returned by such an instruction is in its register by then.
+template <int NI = 8, class Next, class Begin, class Emit, class Early, class UOff = H1PlainUnits, int ABL = 0>
 __device__ __forceinline__ void h16_tile_stream(int row_bytes, int nunits, float *lds, Next next, Begin begin, Emit emit,
-                                                UOff uoff = UOff()) {
+                                                Early early, UOff uoff = UOff()) {
   static_assert(NI == 8 || NI == 4 || NI == 2, "query blocks per wave");
   constexpr int NA = NI == 8 ? 4 : NI;   // query fragments per read / product group
   // NI < 8: a unit holds the 256 corpus rows + the tile's 32 NI query rows only (20 / 24 KiB instead of 32), so the same 128 KiB
@@ -235,12 +238,15 @@ __device__ __forceinline__ void h16_tile_stream(int row_bytes, int nunits, float
       for (int u = 2; u < nunits; u += 2) {
         if (u + 2 >= nunits) begin();
         window_h(u, No(), No(), A0, A1, BL, BH);
+        if (u == DEPTH - 2) early();
         window_h(u + 1, No(), No(), A1, A0, BH, BL);
+        if (u + 1 == DEPTH - 2) early();
       }
       mma(A1, BH, 0, No());
     } else {
     window(0, std::integral_constant<int, 0>(), A0, A1);
     window(1, std::integral_constant<int, 1>(), A1, A0);
+    early();
     for (int u = 2; u < nunits; u += 2) {
       if (u + 2 >= nunits) begin();   // two windows (~2 us) ahead of the epilogue: what begin() loads is not held in registers through the tile
       window(u, std::integral_constant<int, 2>(), A0, A1);

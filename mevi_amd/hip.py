@@ -141,6 +141,7 @@ _SIGNATURES = {
                                        c_int64, ctypes.c_int32, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     "mevi_first_hits_i64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "mevi_ip_filter_tile_walk": (c_int64, [c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "mevi_ip_topk_set_growth": (None, [c_double]),
     "mevi_ip_topk_set_profiling": (None, [c_int]),
     "mevi_ip_topk_get_stats": (None, [ctypes.POINTER(IpTopkStats)]),

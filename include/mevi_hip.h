@@ -389,6 +389,9 @@ int mevi_gemm_nt_rmsnorm_split_to_split(const float *x, int64_t ldx, const float
  *   final_step == 1: out_scores [nq, nb] = beam_score[r] + log_softmax(logits[r])[0] (eos closes)
  *   final_step == 2: pq.beam_search step -- logits f32 [nq*nb, K] (no eos column), candidates
  *       beam_score[r] * softmax(logits[r])[c], outputs as for 0
+ * Limits (refused before any launch): nb*K <= 16384, R <= nb*K (final_step 0 and 2), and one workgroup's LDS --
+ * 8 bytes per sort key (nb*K rounded up to a power of two, at least 64) plus 8 per beam -- at most 160 KiB, so
+ * nb*K = 16384 needs K >= 4.  The same limits hold for mevi_beam_step_tree_f32.
  * ---------------------------------------------------------------------- */
 int mevi_beam_step_f32(const float *logits, const float *beam_scores, int64_t nq, int64_t nb, int64_t K,
                        int64_t R, int final_step, float *out_scores, int32_t *out_parent,
@@ -430,7 +433,8 @@ int mevi_segment_sort_desc_f32(const float *scores, const int64_t *ids, const in
 /* --doc_multiclus > 1 (MEVI/main_models.py:3997-4011: np.unique + the `uscores[ui] += s` / torch.max loop + torch.sort):
  * per segment the entries of one id are merged -- mode 0 'add': 0 + s + s ... in list order (sequential f32 adds),
  * mode 1 'max' -- and the unique entries sorted by (score desc, id asc) into out[seg_offsets[s] ...], out_counts[s] of
- * them.  ids in [0, 2^32), segments of at most 16384 entries. */
+ * them.  ids in [0, 2^32), segments of at most 16384 entries; max_seg_len == 0 only zeroes out_counts (scores and ids
+ * may then be null). */
 int mevi_segment_aggregate_sort_f32(const float *scores, const int64_t *ids, const int64_t *seg_offsets, int64_t nseg,
                                     int64_t max_seg_len, int mode, float *out_scores, int64_t *out_ids,
                                     int32_t *out_counts, void *stream);

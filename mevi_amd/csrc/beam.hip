@@ -16,6 +16,10 @@
 namespace mevi {
 namespace {
 
+// LDS of one workgroup on gfx950: P sort keys (P = nb*K rounded up to a power of two >= 64) plus two floats per
+// beam must fit, so nb*K = 16384 takes at most 4096 beams (K >= 4); K = 1 or 2 at that size is refused.
+constexpr size_t kMaxLds = 160 * 1024;
+
 // mode 0: NCI step (K+1 columns, col 0 = eos, log-domain);  mode 1: NCI final step;
 // mode 2: pq.beam_search step (K columns of -distance): cand = beam_prob[r] * softmax(row)[c]  (pq.py:660-676)
 // Generic prefix trees (TreeBuilder(share_sons=False), MEVI/main_models.py:50-63; the mask walk of
@@ -157,6 +161,8 @@ extern "C" int mevi_beam_step_f32(const float *logits, const float *beam_scores,
   int P = 64;
   while (P < nb * K) P <<= 1;
   const size_t lds = (size_t)P * 8 + (size_t)nb * 8;
+  MEVI_REQUIRE(lds <= kMaxLds, MEVI_ERR_UNSUPPORTED, "beam_step: nb=%lld, K=%lld need %zu bytes of LDS > %zu",
+               (long long)nb, (long long)K, lds, kMaxLds);
   if (lds > 65536)
     MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(beam_step_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -182,6 +188,8 @@ extern "C" int mevi_beam_step_tree_f32(const float *logits, const float *beam_sc
   int P = 64;
   while (P < nb * K) P <<= 1;
   const size_t lds = (size_t)P * 8 + (size_t)nb * 8;
+  MEVI_REQUIRE(lds <= kMaxLds, MEVI_ERR_UNSUPPORTED, "beam_step: nb=%lld, K=%lld need %zu bytes of LDS > %zu",
+               (long long)nb, (long long)K, lds, kMaxLds);
   if (lds > 65536)
     MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(beam_step_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

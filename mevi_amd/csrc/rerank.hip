@@ -164,7 +164,12 @@ extern "C" int mevi_segment_aggregate_sort_f32(const float *scores, const int64_
                                                int32_t *out_counts, void *stream) {
   MEVI_REQUIRE(nseg >= 0 && max_seg_len >= 0 && (mode == 0 || mode == 1), MEVI_ERR_INVALID_ARG, "segment_aggregate_sort: bad arguments");
   if (nseg == 0) return MEVI_OK;
-  MEVI_REQUIRE(scores && ids && seg_offsets && out_scores && out_ids && out_counts, MEVI_ERR_INVALID_ARG, "segment_aggregate_sort: null pointer");
+  MEVI_REQUIRE(out_counts, MEVI_ERR_INVALID_ARG, "segment_aggregate_sort: null pointer");
+  if (max_seg_len == 0) {  // every segment empty (the score / id arrays may be too): nothing to merge
+    MEVI_HIP_CHECK(hipMemsetAsync(out_counts, 0, (size_t)nseg * sizeof(int32_t), (hipStream_t)stream));
+    return MEVI_OK;
+  }
+  MEVI_REQUIRE(scores && ids && seg_offsets && out_scores && out_ids, MEVI_ERR_INVALID_ARG, "segment_aggregate_sort: null pointer");
   MEVI_REQUIRE(max_seg_len <= 16384, MEVI_ERR_UNSUPPORTED, "segment_aggregate_sort: segment of %lld > 16384 entries", (long long)max_seg_len);
   int P = 64;
   while (P < max_seg_len) P <<= 1;

@@ -97,7 +97,7 @@ class FineStage:
 
         aggregate 'add' | 'max' (--doc_multiclus > 1, main_models.py:3997-4011): a document reached through several
         beam clusters is listed once, with the sum (sequential f32 adds, as the reference accumulates) or the maximum
-        of its per-cluster scores -- which are all the same q.d.
+        of its per-cluster scores -- all the same q.d, unless beam_weights give every occurrence its own score.
 
         beam_weights f32[B, R] (--use_topic_model 1, main_models.py:3539-3552,3952: get_inference_scores with
         topic_score_ratio 0): every document's score is its cluster's beam score times q.d (one f32 multiply); with
@@ -128,18 +128,22 @@ class FineStage:
                 s_u, i_u, cnt = ops.segment_aggregate_sort(sc, cand_t, torch.from_numpy(seg), int(ndoc.max()), aggregate)
                 s_u, i_u, cnt = s_u.cpu().numpy(), i_u.cpu().numpy(), cnt.cpu().numpy()
                 return [(i_u[a:a + c], s_u[a:a + c]) for a, c in zip(seg[:-1], cnt)], ndoc
-            # a query with more candidates than the LDS sort holds (rare): the same merge with device-wide sorts
+            # a query with more candidates than the LDS sort holds (rare): the same merge with device-wide sorts.  A
+            # stable sort by (query, doc) keeps each group's entries in candidate order; every group then folds its OWN
+            # scores in that order from 0 ('add') or -inf ('max'), one f32 operation per occurrence -- with beam weights
+            # the occurrences of a document carry different scores.  The loop runs over occurrence ranks (<= R).
             n = self.emb.shape[0]
-            key, inverse, count = torch.unique(cand_q * n + cand_t, sorted=True, return_inverse=True, return_counts=True)
-            one = torch.empty(key.shape, dtype=torch.float32, device=self.dev)
-            one[inverse] = sc                                    # duplicates carry the same bits
-            if aggregate == "add":
-                acc = one.clone()
-                for t in range(1, int(count.max().item())):
-                    acc = torch.where(count > t, acc + one, acc)
-                one = acc
-            sc, cand_t = one, key % n
-            seg_len = torch.bincount(key // n, minlength=B).cpu().numpy()
+            key, order = torch.sort(cand_q * n + cand_t, stable=True)
+            ukey, count = torch.unique_consecutive(key, return_counts=True)
+            first = torch.cumsum(count, 0) - count
+            s_ord = sc[order]
+            acc = torch.full(ukey.shape, 0.0 if aggregate == "add" else -float("inf"), dtype=torch.float32, device=self.dev)
+            for t in range(int(count.max().item())):
+                has = count > t
+                s_t = s_ord[torch.where(has, first + t, first)]
+                acc = torch.where(has, acc + s_t if aggregate == "add" else torch.maximum(acc, s_t), acc)
+            sc, cand_t = acc, ukey % n
+            seg_len = torch.bincount(ukey // n, minlength=B).cpu().numpy()
             seg = np.concatenate([[0], np.cumsum(seg_len)]).astype(np.int64)
         longest = int(seg_len.max())
         if longest <= MAX_SEGMENT:

@@ -439,6 +439,30 @@ int mevi_segment_aggregate_sort_f32(const float *scores, const int64_t *ids, con
                                     int64_t max_seg_len, int mode, float *out_scores, int64_t *out_ids,
                                     int32_t *out_counts, void *stream);
 
+/* --query_encoder nci (T5FineTuner.clus_repr, MEVI/main_models.py:1998-2047, called with flatten=True): the query
+ * embedding of every (query, beam) pair, out f32 [B*R, dim] (row stride ldo), row q*R + j pooled over
+ *   MEVI_QPOOL_ENC / _ENCMASK  rows 0..S-1 of enc[q] (enc f32 [B, S, dim], strides enc_ldb / enc_lds; read once per query);
+ *                              ENCMASK applies mask i64 [B, mask_ld] as the reference does, plain ENC pools pad rows too
+ *   MEVI_QPOOL_DEC             positions t = 0..T-1: row anc[(q*R + j) * T + t] of dec + t * dec_ldt (row stride dec_ldr,
+ *                              dec_rows rows per step) -- the per-step decoder outputs and the beams' ancestor table
+ *   MEVI_QPOOL_EMB             row emb_ids[q*R + j] of emb_table [emb_rows, emb_ld]
+ * with MEVI_QPOOL_MAX (torch.max), _AVG (mean; masked: sum / (valid rows + T + emb)) or _ATTEN (softmax of
+ * <h, atten_w> + atten_b over the rows, then the weighted sum).  dim % 4 == 0, S <= 512, T <= 9, R <= 64; rows
+ * 16-byte aligned.  MAX is exact; AVG / ATTEN error bounds: DESIGN.md section 4.  Stream-ordered. */
+#define MEVI_QPOOL_ENC 1
+#define MEVI_QPOOL_ENCMASK 2
+#define MEVI_QPOOL_DEC 4
+#define MEVI_QPOOL_EMB 8
+#define MEVI_QPOOL_MAX 0
+#define MEVI_QPOOL_AVG 16
+#define MEVI_QPOOL_ATTEN 32
+#define MEVI_QPOOL_ACCUM_MASK 48
+int mevi_query_pool_f32(const float *enc, int64_t enc_ldb, int64_t enc_lds, const int64_t *mask, int64_t mask_ld,
+                        int64_t B, int64_t S, const float *dec, int64_t dec_ldt, int64_t dec_ldr, int64_t dec_rows,
+                        const int32_t *anc, int64_t T, const int64_t *emb_ids, const float *emb_table, int64_t emb_ld,
+                        int64_t emb_rows, int64_t R, int64_t dim, int mode, const float *atten_w, float atten_b,
+                        float *out, int64_t ldo, void *stream);
+
 /* Pieces of pq.beam_search (MEVI/pq.py:613-713; only reached with doc_multiclus > 1): the score row
  * -sum_k (x_k - c_k)^2 of every row against the K centroids of one level, and the residual hand-down
  * out[r] = x[src[r]] - centroids[code[r]].  The top-R step is mevi_beam_step_f32 with final_step = 2

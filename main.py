@@ -2,7 +2,7 @@
 """`python main.py --mode eval ...` -- the argv surface of the reference's MEVI/main.py for the eval
 path that marco_eval_nci_rq.sh drives (MEVI/main.py:356-794, 267-337).  Every flag of that script is
 accepted; the ones that configure training are parsed and ignored.  Only --mode eval with
---codebook 1 --pq_type rq --document_encoder ance|cocondenser|ar2 --query_encoder twin --recall_level both|coarse|fine is built
+--codebook 1 --pq_type rq --document_encoder ance|cocondenser|ar2 --query_encoder twin|nci --recall_level both|coarse|fine is built
 (+ the brute-force ablation --eval_all_documents 1 --recall_level fine --knn_topk_by_step 1)
 (the configuration of every shipped eval script); anything else raises.
 
@@ -93,6 +93,12 @@ def parsers_parser(argv=None):
             raise SystemExit(f"main.py --mode eval: --{name} {value} changes what is evaluated and is not built "
                              f"(built: {' | '.join(allowed)})")
         ignored.append(("--" + name, value))
+    # --qtower / --query_embed_accum (MEVI/main.py:533-534) are read by --query_encoder nci only; other runs ignore them
+    given = dict(ignored)
+    args.qtower = given.get("--qtower", "enc_dec")
+    args.query_embed_accum = given.get("--query_embed_accum", "maxpool")
+    if args.query_encoder == "nci":
+        ignored = [f for f in ignored if f[0] not in ("--qtower", "--query_embed_accum")]
     args.ignored_flags = ignored
     args.recall_num = sorted(int(r) for r in args.recall_num.split(","))
     if not args.document_encoder or args.recall_level == "coarse":      # MEVI/main.py:750-752
@@ -176,7 +182,11 @@ def check_supported(a):
         raise SystemExit(f"main.py --mode eval: --test_set {a.test_set!r} is not built (only 'dev')")
     if a.dataset not in ("marco", "nq_dpr"):
         raise SystemExit(f"main.py --mode eval: --dataset {a.dataset!r} is not built (marco, nq_dpr)")
-    need = dict(codebook=1, pq_type="rq", query_encoder="twin")
+    need = dict(codebook=1, pq_type="rq")
+    if a.query_encoder == "nci":
+        check_nci_query_encoder(a)
+    elif a.query_encoder != "twin":
+        raise SystemExit(f"main.py --mode eval: --query_encoder {a.query_encoder!r} is not built (twin | nci)")
     if a.recall_level not in ("both", "coarse", "fine"):
         raise SystemExit(f"main.py --mode eval: --recall_level {a.recall_level!r} is not built (both | coarse | fine)")
     if a.doc_multiclus < 1 or (a.doc_multiclus > 1 and (a.eval_all_documents or a.knn_topk_by_step)):
@@ -194,6 +204,35 @@ def check_supported(a):
     if a.num_return_sequences > (2 ** a.subvector_bits) ** a.subvector_num:
         raise SystemExit("num_return_sequences exceeds the number of code paths (2**subvector_bits)**subvector_num: the "
                          "reference would return -1e9 placeholder hypotheses")
+
+
+QTOWER_PIECES = ("enc", "encmask", "dec", "emb")
+
+
+def check_nci_query_encoder(a):
+    """--query_encoder nci: the fine stage scores with T5FineTuner.clus_repr's pool of the NCI model's own hidden states
+    (MEVI/main_models.py:1975-2047).  Built for any '_'-joined subset of enc / encmask / dec / emb and the three accums."""
+    pieces = a.qtower.split("_")
+    if "ori" in pieces:
+        raise SystemExit("main.py --mode eval --query_encoder nci: --qtower with 'ori' needs --reserve_decoder (not built)")
+    bad = [p for p in pieces if p not in QTOWER_PIECES]
+    if bad or not a.qtower:
+        raise SystemExit(f"main.py --mode eval --query_encoder nci: --qtower {a.qtower!r} has unknown pieces {bad} "
+                         f"(built: '_'-joined subsets of {' '.join(QTOWER_PIECES)})")
+    if a.query_embed_accum.lower() not in ("maxpool", "avgpool", "attenpool"):
+        raise SystemExit(f"main.py --mode eval --query_encoder nci: --query_embed_accum {a.query_embed_accum!r} is not built "
+                         "(maxpool | avgpool | attenpool)")
+    if a.save_hard_neg:         # MEVI/main.py:642-646
+        raise SystemExit("main.py --mode eval --query_encoder nci: --save_hard_neg > 0 needs --query_encoder twin (the reference asserts it)")
+    if a.eval_all_documents:    # MEVI/main.py:657-658
+        raise SystemExit("main.py --mode eval --query_encoder nci: --eval_all_documents needs --query_encoder twin (the reference asserts it)")
+    if a.query_embedding_path:
+        raise SystemExit("main.py --mode eval --query_encoder nci: --query_embedding_path holds tower embeddings; nci pools "
+                         "the NCI model's own states per beam")
+    if a.query_embed_accum.lower() == "attenpool" and a.infer_ckpt is None:
+        raise SystemExit("main.py --mode eval --query_encoder nci: --query_embed_accum attenpool needs --infer_ckpt (the "
+                         "attenpool_weight projection lives in the whole-model checkpoint; with --nci_ckpt alone the "
+                         "reference would use an untrained, randomly initialised projection)")
 
 
 def _free_port():

@@ -18,6 +18,7 @@ import torch
 from . import dense as mdense
 from . import fine as mfine
 from . import hip
+from . import ops
 from .io import RankLog, encode_batch, join_i64, load_checkpoint, upload_rows
 from .phases import mark
 from .nci import MODEL_INFO, NCIModel, check_weights, config_from_weights, decode_token
@@ -75,6 +76,15 @@ def split_whole_checkpoint(sd, not_load_document_encoder=False):
     pre = "document_encoder.lm_q."
     tower = {} if not_load_document_encoder else {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
     return nci_w, tower, sd.get("pq.codebook")
+
+
+def attenpool_from_checkpoint(sd):
+    """--query_encoder nci --query_embed_accum attenpool: the Linear(d_model, 1) `attenpool_weight` of a whole-model
+    checkpoint (T5FineTuner.__init__, MEVI/main_models.py:1314-1315) -> (w f32 [d], b float)."""
+    if "attenpool_weight.weight" not in sd or "attenpool_weight.bias" not in sd:
+        raise SystemExit("--query_embed_accum attenpool: the --infer_ckpt checkpoint has no attenpool_weight.weight / .bias")
+    w, b = sd["attenpool_weight.weight"], sd["attenpool_weight.bias"]
+    return w.detach().float().reshape(-1).contiguous(), float(b.reshape(-1)[0])
 
 
 def load_hf_state_dict(model_dir):
@@ -283,15 +293,26 @@ class EvalRun:
         a = args
         self.M, self.K, self.R = a.subvector_num, 2 ** a.subvector_bits, a.num_return_sequences
         tower_override, ckpt_codebook = {}, None
+        # --query_encoder nci: the fine stage pools the NCI model's own states per (query, beam) (T5FineTuner.clus_repr);
+        # the query tower is neither loaded nor run
+        self.nci_query = getattr(a, "query_encoder", "twin") == "nci"
+        if self.nci_query:
+            self.qpool_mode = ops.qpool_mode(a.qtower, a.query_embed_accum)
+            self.atten = None
         # The 27 GB corpus upload (file reads + PCIe: ~0.8 s, 8 reader threads) and the checkpoint loads / model build below
         # (one Python thread: ~0.8 s) need different resources: the upload starts NOW on a background thread and is joined
         # where `self.emb` is first needed.  Only when the row width is known without loading the tower (T5-ANCE: config.json).
         emb_job = self._start_corpus_upload(a)
         if getattr(a, "infer_ckpt", None):        # whole-model checkpoint (MEVI/main.py:203-230) takes precedence
-            nci_w, tower_override, ckpt_codebook = split_whole_checkpoint(
-                _state_dict(a.infer_ckpt), bool(getattr(a, "not_load_document_encoder", 0)))
+            sd = _state_dict(a.infer_ckpt)
+            nci_w, tower_override, ckpt_codebook = split_whole_checkpoint(sd, bool(getattr(a, "not_load_document_encoder", 0)))
+            if self.nci_query and self.qpool_mode & ops.QPOOL_ACCUM["attenpool"]:
+                self.atten = attenpool_from_checkpoint(sd)
+            del sd
         else:
             nci_w = load_nci_weights(a.nci_ckpt)
+        if self.nci_query and self.qpool_mode & ops.QPOOL_ACCUM["attenpool"] and self.atten is None:
+            raise SystemExit("--query_encoder nci --query_embed_accum attenpool needs --infer_ckpt (its attenpool_weight)")
         self.cfg = config_from_weights(nci_w, self.M, self.K)
         info = MODEL_INFO.get(getattr(a, "model_info", None))
         if info is not None and info[3] == self.cfg.d_model:
@@ -312,7 +333,9 @@ class EvalRun:
         # the tower and its tokenizer (init_document_encoder, MEVI/main_models.py:1643-1681)
         enc = getattr(a, "document_encoder", None) or "ance"
         tower_dir = os.path.join(a.ckpt_dir, "t5-ance")       # NCI shares the T5-ANCE vocabulary in every configuration
-        if enc == "ance":
+        if self.nci_query:
+            self.tower = None
+        elif enc == "ance":
             tw, tdims = load_tower_weights(tower_dir)
             tw.update(tower_override)             # document_encoder.lm_q.* of a whole-model checkpoint
             self.tower = TwinTower(tw, dims=tdims, device=self.dev)
@@ -333,14 +356,15 @@ class EvalRun:
         # bert-base-uncased, special tokens only for 'ar2' (main_models.py:359-360)
         self.tower_tokenizer = tower_tokenizer
         self.tower_special_tokens = enc in ("ance", "ar2")
-        if enc != "ance" and tower_tokenizer is None:
+        if enc != "ance" and tower_tokenizer is None and not self.nci_query:
             from transformers import AutoTokenizer
 
             local = os.path.join(a.ckpt_dir, "bert-base-uncased")
             self.tower_tokenizer = AutoTokenizer.from_pretrained(local if os.path.isdir(local) else "bert-base-uncased",
                                                                  do_lower_case=True)
         # corpus embeddings resident in HBM (the reference keeps a CPU memmap and copies per cluster)
-        d_model = self.tower.dim     # the corpus embeddings and the RQ codebook live in the tower's output space
+        # the corpus embeddings and the RQ codebook live in the query embedding's space: the tower's, or the NCI model's
+        d_model = self.cfg.d_model if self.nci_query else self.tower.dim
         n_docs = os.path.getsize(a.embedding_path) // (4 * d_model)
         if emb_job is not None and emb_job[1] == d_model:
             emb_job[0].join()
@@ -594,16 +618,19 @@ class EvalRun:
         if timing:
             torch.cuda.synchronize()
             t0 = time.time()
-        decoded, scores, _, _ = self.nci.generate(ids, mask, num_beams=R, num_return_sequences=R,
-                                                  length_penalty=a.length_penalty, max_length=self.M + 2, graph=timing,
-                                                  decode_tree=self.decode_tree())
+        want_c, want_f = self.level in ("coarse", "both"), self.level in ("fine", "both")
+        keep = self.nci_query and want_f
+        # plain `enc` pools the padded positions too: their states must be the reference's, not the packed encoder's zeros
+        pad = keep and bool(self.qpool_mode & ops.QPOOL_PIECES["enc"]) and not self.qpool_mode & ops.QPOOL_PIECES["encmask"]
+        decoded, scores, enc_h, dec_h = self.nci.generate(ids, mask, num_beams=R, num_return_sequences=R,
+                                                          length_penalty=a.length_penalty, max_length=self.M + 2, graph=timing,
+                                                          decode_tree=self.decode_tree(), output_dec_hidden=keep, pad_encoder=pad)
         B = len(texts)
         codes = decode_token(decoded, self.K).view(B, R, self.M).cpu().numpy()
         scores = np.array(scores).reshape(B, R)
         if timing:
             t1 = time.time()
             self.timer["nci"].append(t1 - t0)
-        want_c, want_f = self.level in ("coarse", "both"), self.level in ("fine", "both")
         if not want_f:      # recall_level 'coarse': cluster ranks and the candidate count only (main_models.py:3736-3780)
             ndoc = self.fine.candidates_device(codes)[3]
             results = []
@@ -613,7 +640,10 @@ class EvalRun:
                 self.coarse_log.add((text, d, gt_codes, scores[i].tolist()) if self.nq is None else (text, d, scores[i].tolist()))
                 results.append((text, int(ndoc[i]), cr))
             return self._timed(results, t1 if timing else None)
-        qemb = self.query_embedding(texts, ids, mask, rows)
+        if keep:
+            qemb = self.nci_query_embedding(decoded, enc_h, mask, dec_h)
+        else:
+            qemb = self.query_embedding(texts, ids, mask, rows)
         weights = None
         if self.topic:      # nci_scores: the beam scores, or ones for a single returned sequence (main_models.py:3678-3682)
             weights = torch.ones((B, 1), dtype=torch.float32) if R == 1 else torch.tensor(scores, dtype=torch.float32)
@@ -647,6 +677,15 @@ class EvalRun:
                                  mfine.f32_repr(sc[:n])))
             results.append((text, int(ndoc[i]), cr, fr) if want_c else (text, int(ndoc[i]), fr))
         return self._timed(results, t1 if timing else None)
+
+    def nci_query_embedding(self, decoded, enc_h, mask, dec_h):
+        """--query_encoder nci: clus_repr(enc, mask, None, dec_hidden, lm_labels = decoded[:, -2], flatten=True)
+        (main_models.py:3800-3812) -> f32 [B*R, d], row q*R + j paired with the query's j-th (sorted) beam cluster."""
+        w, b = self.atten if self.atten is not None else (None, 0.0)
+        if w is not None:
+            w = w.to(self.dev)
+        return ops.query_pool(self.qpool_mode, self.R, enc=enc_h, mask=mask, dec=(dec_h.steps, dec_h.anc),
+                              emb_ids=decoded[:, -2], emb_table=self.nci.dec_emb, atten_w=w, atten_b=b)
 
     def _coarse_ranks(self, d, gts):
         """Ranks of a sample's gt clusters among its beam clusters `d` (+ the gt codes the coarse log prints)."""

@@ -92,7 +92,8 @@ class FineStage:
         return cand, cand_q, seg, ndoc
 
     def rerank(self, query_emb, beam_codes, aggregate=None, beam_weights=None, doc_proba=None, ratio=0.0, beam_recon=None):
-        """query_emb f32[B, dim] (CUDA).  Returns per query: (doc ids i64 ndarray, scores f32 ndarray) -- views of
+        """query_emb f32[B, dim] (CUDA), or f32[B * R, dim] (--query_encoder nci: every (query, beam) pair has its own
+        embedding; candidate t of beam j of query q is scored with row q * R + j).  Returns per query: (doc ids i64 ndarray, scores f32 ndarray) -- views of
         one host copy of the sorted batch --, and ndoc (candidates incl. repeats).
 
         aggregate 'add' | 'max' (--doc_multiclus > 1, main_models.py:3997-4011): a document reached through several
@@ -110,7 +111,10 @@ class FineStage:
         B = len(ndoc)
         if cand_t.numel() == 0:
             return [(np.zeros(0, np.int64), np.zeros(0, np.float32)) for _ in range(B)], ndoc
-        sc = ops.pair_dot(query_emb, cand_q, self.emb, cand_t)
+        R = np.shape(beam_codes)[1]
+        per_beam = query_emb.shape[0] != B
+        assert not per_beam or query_emb.shape[0] == B * R, (tuple(query_emb.shape), B, R)
+        sc = ops.pair_dot(query_emb, cand_q * R + cand_beam if per_beam else cand_q, self.emb, cand_t)
         if beam_weights is not None:
             w = torch.as_tensor(beam_weights, dtype=torch.float32, device=self.dev)
             if beam_recon is not None and ratio:

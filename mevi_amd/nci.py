@@ -430,12 +430,15 @@ class NCIModel:
             self._graphs = GraphCache()     # captured generate() graphs hold the old tables' addresses and level structure
 
     # -- one decoding position for all live beams -----------------------------------------------
-    def _logits(self, tokens, t, dcache, acache, xkv, mask, kv_div, pidx=None, key_rows=None):
+    def _logits(self, tokens, t, dcache, acache, xkv, mask, kv_div, pidx=None, key_rows=None, keep=None):
         """pidx: the beams' prefix indices at position t when the prefix tables cover it (acache unused then).
-        key_rows: ancestor-indexed decoder caches (DecoderStack.step)."""
+        key_rows: ancestor-indexed decoder caches (DecoderStack.step).  keep: f32 [n, d] that receives the decoder
+        stack's output (after final_layer_norm, before the alpha scale) -- the dec_hidden rows of --query_encoder nci."""
         c = self.cfg
         tok = ops.gather_rows(self.dec_emb, tokens)
         seq = self.decoder.step(tok, t, dcache, xkv, mask, kv_div, key_rows=key_rows)
+        if keep is not None:
+            keep.copy_(seq)
         alpha = c.d_model ** -0.5                                  # modeling_t5.py:1607, applied inside the logits kernel
         if not ROW_LOGITS:
             seq = ops.scale(seq, alpha)
@@ -459,10 +462,13 @@ class NCIModel:
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask, num_beams=10, num_return_sequences=None, length_penalty=0.8,
-                 max_length=None, graph=False, **reference_kwargs):
+                 max_length=None, graph=False, output_dec_hidden=False, pad_encoder=False, **reference_kwargs):
         """Returns (decoded i64[B*R, M+2], scores list[float] (descending per query),
-        enc_last_hidden_state f32[B*R, S, d] view, None) like the reference's 4-tuple; the last slot
-        (dec_hidden) is only read when query_encoder='nci' and is not produced (SURVEY 8(a') note iii).
+        enc_last_hidden_state f32[B*R, S, d] view, dec_hidden) like the reference's 4-tuple.  dec_hidden (read only by
+        --query_encoder nci) is None unless output_dec_hidden: then a DecHidden -- the decoder states of every beam at
+        positions 0..M in the reference's row order, the beams as they entered the final step, BEFORE the hypotheses are
+        sorted by score (decoded / scores are after that sort: row q*R + j of the two may belong to different beams).
+        pad_encoder: run the padded encoder (pad rows hold the reference's values, not 0; graph=True always does).
         graph=True (batches of at most GRAPH_MAX_ROWS queries): replay the whole search as one captured HIP graph
         (fixed shapes: padded encoder, no host synchronisation inside) -- same kernels, same results, no host jitter;
         the median latency is the kernels' own time either way (tools/bench_latency.py)."""
@@ -486,11 +492,13 @@ class NCIModel:
         if graph and 0 < ids.shape[0] <= GRAPH_MAX_ROWS:
             if self.prefix_table_bytes:
                 self.tables(R)
-            decoded, hyp, enc = self._graphs.run(("generate", R, float(length_penalty), id(tree)) + tuple(ids.shape),
-                                                 lambda i, m: self._search(i, m, R, length_penalty, pack=False, tree=tree), ids, mask)
+            out = self._graphs.run(("generate", R, float(length_penalty), id(tree), bool(output_dec_hidden)) + tuple(ids.shape),
+                                   lambda i, m: self._search(i, m, R, length_penalty, pack=False, tree=tree,
+                                                             keep_dec=output_dec_hidden), ids, mask)
         else:
-            decoded, hyp, enc = self._search(ids, mask, R, length_penalty, pack=True, tree=tree)
-        return decoded, hyp.reshape(-1).tolist(), enc, None
+            out = self._search(ids, mask, R, length_penalty, pack=not pad_encoder, tree=tree, keep_dec=output_dec_hidden)
+        decoded, hyp, enc = out[:3]
+        return decoded, hyp.reshape(-1).tolist(), enc, DecHidden(*out[3:]) if output_dec_hidden else None
 
     @torch.no_grad()
     def generate_all(self, input_ids, attention_mask, length_penalty=0.8, max_rows=1 << 16):
@@ -559,8 +567,9 @@ class NCIModel:
         zeros = torch.zeros(nq, dtype=torch.int64, device=self.dev)
         expand(0, xkv, 1, 0, zeros, zeros, torch.zeros(nq, dtype=torch.float32, device=self.dev), self.decoder.new_cache(nq), None)
 
-    def _search(self, ids, mask, R, length_penalty, pack, tree=None):
-        """The device part of generate(): (decoded i64[B*R, M+2], hypothesis scores f64[B, R], encoder states).
+    def _search(self, ids, mask, R, length_penalty, pack, tree=None, keep_dec=False):
+        """The device part of generate(): (decoded i64[B*R, M+2], hypothesis scores f64[B, R], encoder states) and, with
+        keep_dec, (every step's decoder output f32 [M+1, rows, d], the final beams' ancestor rows i32 [B*R, M+1]).
         `tree` (a PrefixTree): beams continue along the trie's children only (mevi_beam_step_tree_f32).  The reference then
         runs all R beams from the first step, beams 1..R-1 seeded with -1e9 (generation_utils.py:752-756): they follow the
         same trie and fill the slots real candidates cannot whenever fewer than R exist -- so does this search (every beam
@@ -588,6 +597,9 @@ class NCIModel:
         anc = torch.zeros((B * nb, 0), dtype=torch.int32, device=self.dev)
         acache = self.adaptor.new_cache(B * nb) if levels == 0 else None
         base = torch.arange(B, device=self.dev)[:, None]
+        if keep_dec:     # step p's output of row r stays in steps[p, r]; hanc names each live beam's rows (as `anc` does)
+            steps = torch.empty((c.M + 1, B * (min(R, c.K ** c.M) if tree is None else R), c.d_model), dtype=torch.float32, device=self.dev)
+            hanc = torch.zeros((B * nb, 0), dtype=torch.int32, device=self.dev)
         for p in range(c.M + 1):
             if p == levels and p > 0:       # first position beyond the tables: its cache comes from them
                 if p == c.M and p <= 7 and INDEXED_ADAPTOR_CACHE:   # ... in place, when no later position continues from it (<= 8 keys)
@@ -597,7 +609,11 @@ class NCIModel:
             key_rows = None
             if indexed:
                 key_rows = torch.cat([anc, torch.arange(anc.shape[0], dtype=torch.int32, device=self.dev)[:, None]], 1).contiguous()
-            logits = self._logits(tokens, p, dcache, acache, xkv, mask, nb, pidx if p < levels else None, key_rows=key_rows)
+            if keep_dec:
+                hrows = key_rows if indexed else \
+                    torch.cat([hanc, torch.arange(hanc.shape[0], dtype=torch.int32, device=self.dev)[:, None]], 1).contiguous()
+            logits = self._logits(tokens, p, dcache, acache, xkv, mask, nb, pidx if p < levels else None, key_rows=key_rows,
+                                  keep=steps[p, :tokens.numel()] if keep_dec else None)
             if p == c.M:
                 break
             Rp = min(R, nb * c.K)                                             # beams alive after this level
@@ -607,6 +623,8 @@ class NCIModel:
                 scores, parent, code, node = ops.beam_step_tree(logits, scores, c.K, Rp, node, tree.mask[p], tree.base[p])
             parent, code = parent.long(), code.long()
             rows = (base * nb + parent).reshape(-1)                           # surviving parents, [B*Rp]
+            if keep_dec:
+                hanc = hrows[rows]
             if indexed:
                 anc = key_rows[rows]
             else:
@@ -630,7 +648,23 @@ class NCIModel:
         toks = 2 + torch.arange(c.M, device=self.dev) * c.K + codes
         decoded = torch.cat([torch.zeros((B, R, 1), dtype=torch.int64, device=self.dev), toks,
                              torch.ones((B, R, 1), dtype=torch.int64, device=self.dev)], dim=2).view(B * R, c.M + 2)
+        if keep_dec:
+            return decoded, hyp, enc, steps, hrows
         return decoded, hyp, enc
+
+
+class DecHidden:
+    """generate()'s dec_hidden slot without the [B*R, M+1, d] copy: `steps` f32 [M+1, rows, d] holds the decoder output of
+    step t's row r at steps[t, r]; `anc` i32 [B*R, M+1] names, per final beam (pre-sort order), the row of each position.
+    ops.query_pool gathers through the table itself; dense() materialises the reference's tensor."""
+
+    __slots__ = ("steps", "anc")
+
+    def __init__(self, steps, anc):
+        self.steps, self.anc = steps, anc
+
+    def dense(self):
+        return torch.stack([self.steps[t][self.anc[:, t].long()] for t in range(self.anc.shape[1])], 1)
 
 
 def _slice_cross_kv(xkv, a, b):

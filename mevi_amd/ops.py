@@ -804,3 +804,72 @@ def segment_aggregate_sort(scores, ids, seg_offsets, max_seg_len, mode):
                                                    hip.stream_ptr())
     hip.check(st, "mevi_segment_aggregate_sort_f32")
     return out_s, out_i, counts
+
+
+QPOOL_PIECES = {"enc": 1, "encmask": 2, "dec": 4, "emb": 8}
+QPOOL_ACCUM = {"maxpool": 0, "avgpool": 16, "attenpool": 32}
+
+
+def qpool_mode(qtower, accum):
+    """The MEVI_QPOOL_* mode of `--qtower` (split on '_', membership as T5FineTuner.clus_repr tests it) and
+    `--query_embed_accum`.  'ori' (--reserve_decoder) is not built."""
+    pieces = qtower.split("_") if isinstance(qtower, str) else list(qtower)
+    bad = [p for p in pieces if p not in QPOOL_PIECES]
+    if bad or not pieces:
+        raise ValueError(f"qtower {qtower!r}: pieces must be a subset of {sorted(QPOOL_PIECES)}")
+    if accum.lower() not in QPOOL_ACCUM:
+        raise ValueError(f"query_embed_accum {accum!r}: one of {sorted(QPOOL_ACCUM)}")
+    mode = 0
+    for p in pieces:
+        mode |= QPOOL_PIECES[p]
+    return mode | QPOOL_ACCUM[accum.lower()]
+
+
+@hip.on_device
+def query_pool(mode, R, enc=None, mask=None, dec=None, emb_ids=None, emb_table=None, atten_w=None, atten_b=0.0, out=None):
+    """--query_encoder nci query embeddings f32 [B*R, d] (csrc/query_pool.hip).  enc f32 [B, S, d] (NOT expanded over the
+    beams), mask i64 [B, S]; dec = (steps f32 [T, rows, d], anc i32 [B*R, T]): row anc[i, t] of steps[t] is position t of
+    beam row i; emb_ids i64 [B*R] rows of emb_table [V, d]; atten_w f32 [d], atten_b a float."""
+    has_enc, has_dec, has_emb = bool(mode & 3), bool(mode & 4), bool(mode & 8)
+    B = d = None
+    if has_enc:
+        assert enc.dim() == 3 and enc.stride(2) == 1, (enc.shape, enc.stride())
+        B, S, d = enc.shape
+        _f32(enc)
+        if mode & 2:
+            mask = mask.to(device=enc.device, dtype=torch.int64).contiguous()
+            assert mask.shape == (B, S)
+    if has_dec:
+        steps, anc = dec
+        _f32(steps)
+        assert steps.dim() == 3 and steps.stride(2) == 1 and anc.dtype == torch.int32 and anc.is_contiguous()
+        T, rows, d_ = steps.shape
+        assert anc.shape[1] == T and (d is None or d == d_)
+        d = d_
+        if B is None:
+            B = anc.shape[0] // R
+        assert anc.shape[0] == B * R
+    if has_emb:
+        _f32(emb_table)
+        emb_ids = emb_ids.to(device=emb_table.device, dtype=torch.int64).contiguous()
+        assert emb_table.stride(1) == 1 and (d is None or emb_table.shape[1] == d)
+        d = emb_table.shape[1]
+        if B is None:
+            B = emb_ids.numel() // R
+        assert emb_ids.numel() == B * R
+    dev = (enc if has_enc else steps if has_dec else emb_table).device
+    if mode & 48 == 32:
+        atten_w = _f32(atten_w).reshape(-1).contiguous()
+        assert atten_w.numel() == d
+    if out is None:
+        out = torch.empty((B * R, d), dtype=torch.float32, device=dev)
+    st = hip.lib().mevi_query_pool_f32(
+        hip.ptr(enc) if has_enc else None, enc.stride(0) if has_enc else 0, enc.stride(1) if has_enc else 0,
+        hip.ptr(mask) if mode & 2 else None, mask.stride(0) if mode & 2 else 0, B, S if has_enc else 0,
+        hip.ptr(steps) if has_dec else None, steps.stride(0) if has_dec else 0, steps.stride(1) if has_dec else 0,
+        rows if has_dec else 0, hip.ptr(anc) if has_dec else None, T if has_dec else 0,
+        hip.ptr(emb_ids) if has_emb else None, hip.ptr(emb_table) if has_emb else None, emb_table.stride(0) if has_emb else 0,
+        emb_table.shape[0] if has_emb else 0, R, d, mode, hip.ptr(atten_w) if mode & 48 == 32 else None, float(atten_b),
+        hip.ptr(out), out.stride(0), hip.stream_ptr())
+    hip.check(st, "mevi_query_pool_f32")
+    return out

@@ -1163,7 +1163,9 @@ __global__ __launch_bounds__(256) void split_rows_ssq_kernel(const float *__rest
   }
   if (lane == 0) {
     exps[r] = (signed char)e;
-    bound[r] = sqrtf(ss * 0.25f) * 1.001f + mx * 1e-6f;   // ss counts every block four times (all four lanes add the block's sum)
+    // ss counts every block four times (all four lanes add the block's sum).  The l2 norm is >= mx unless the squares underflow
+    // (rows below ~1e-19): then mx itself, so that the bound the stream carries never sits under the row
+    bound[r] = fmaxf(sqrtf(ss * 0.25f) * 1.001f + mx * 1e-6f, mx);
   }
 }
 

@@ -290,11 +290,20 @@ def linear(x, weight, bias=None, residual=None, relu=False, out=None, gelu=False
 # tower 1.33 -> 1.29 ms, NCI 3.11 -> 3.05 ms), and a row must have the same bits in any batch, so there is no folding small batches
 # only.  MEVI_FOLD_NORM=1 turns it on (A/B; tests/test_t5_gpu.py runs the goldens both ways).
 FOLD_NORM = os.environ.get("MEVI_FOLD_NORM", "0") == "1"
+# Widest stack that folds.  At t5-base width (768) the folded encoder block misses the float64 bar of tests/test_t5_f64_gpu.py
+# (4x the f32 restatement's error + 2^-22 max): 9.2e-5 against 8.7e-5 (f32: 1.7e-5, the default path 4.2e-5), on the row of an
+# all-zero embedding.  The stream's image takes its exponent from the carried bound x_bound + ||ctx|| wnorm_max, and the
+# attention context's ||ctx|| is the per-element Cauchy-Schwarz bound times sqrt(d): after one attention sub-layer it sits 7.6
+# binades (median) and up to 11.8 above the row's max, so the next projection reads the row with that many bits fewer.  The
+# kernels themselves meet their float64 contracts up to 1024 (tests/test_gemm_split_gpu.py); the miniature goldens fold.
+FOLD_NORM_MAX_WIDTH = 512
 
 
 def fold_norm_ok(d_model):
-    """Whether the T5 stacks of width d_model run with their norms folded: split GEMM, a width the stream kernels take."""
-    return bool(FOLD_NORM and GEMM_MODE == "split" and hip.lib().mevi_gemm_norm_fold_supported(int(d_model)))
+    """Whether the T5 stacks of width d_model run with their norms folded: split GEMM, a width the stream kernels take, and
+    not wider than FOLD_NORM_MAX_WIDTH (where the folded blocks meet the float64 bars)."""
+    return bool(FOLD_NORM and GEMM_MODE == "split" and int(d_model) <= FOLD_NORM_MAX_WIDTH
+                and hip.lib().mevi_gemm_norm_fold_supported(int(d_model)))
 
 
 def fold_weight(w, ln):

@@ -203,3 +203,187 @@ def hip_lib():
     from mevi_amd import hip
 
     return hip.lib()
+
+
+# ---- the folded T5LayerNorm (ops.ResidualRows: residual_start, linear_normed, linear_residual) against float64 ----------------------
+# Bars: the image of a stream row decodes to x within 2^-21 of the binade of the row's exponent (2^(15 - e) is the power of two above
+# the bound the exponent was taken from); bound >= max |row|; a 16-column block sum of squares is an f32 fma chain of 4 plus two adds,
+# within 8 f32 ulps of the float64 sum of the same 16 f32 values (f32-rounded: rows of 1e30 overflow to inf in f32, as in the
+# reference's own x.pow(2)); products under the GEMM bar 2e-6 sum |a||w| -- with the norm folded, |a| is |rmsnorm(x)| and the f32 row
+# scale adds a few ulps of |y| <= that sum.
+
+
+def _stream_rows(M, D, g, extremes=True):
+    """Rows with the residual stream's statistics: scale 5-20, a handful of channels 50-100x the rest; zero rows and rows of
+    1e-30 / 1e30 when `extremes`."""
+    x = torch.randn((M, D), device="cuda", generator=g) * (5 + 15 * torch.rand((M, 1), device="cuda", generator=g))
+    x[:, [c for c in (3, 100, 401, 700, 1000) if c < D]] *= 75
+    if extremes and M >= 4:
+        x[1] = 0
+        x[2] *= 1e-30
+        x[3] *= 1e30
+    return x
+
+
+def _check_stream(r, x64=None, tag=""):
+    """image vs x, bound >= max |row|, ssq vs float64 of the returned (or given) f32 rows."""
+    x = r.x.double()
+    D = r.x.shape[1]
+    img = _image_value(ops.SplitRows(r.img, r.exp, D))
+    binade = torch.exp2(15 - r.exp.double())[:, None]
+    assert ((img - x).abs() <= 2.0 ** -21 * binade).all(), tag
+    assert (r.bound.double() >= x.abs().amax(1)).all(), tag
+    ref = (x.view(x.shape[0], D // 16, 16) ** 2).sum(2).float().double()
+    got = r.ssq.double()
+    inf = torch.isinf(ref)
+    assert torch.equal(torch.isinf(got), inf), tag
+    assert ((got - ref).abs()[~inf] <= 8 * 2.0 ** -24 * ref[~inf] + 2.0 ** -140).all(), tag
+    if x64 is not None:
+        assert torch.equal(r.x, x64.float()) if x64.dtype == torch.float32 else True
+
+
+@pytest.mark.parametrize("D", [16, 32, 768, 1024])
+def test_residual_start_image_bound_and_block_sums(cuda, D):
+    """mevi_split_rows_ssq_f16: ragged row counts, a strided ldx, zero rows, rows of 1e-30 / 1e30."""
+    g = torch.Generator(device=cuda).manual_seed(D)
+    for M in (1, 7, 333):
+        x = _stream_rows(M, D, g)
+        r = ops.residual_start(x)
+        assert r.ssq.shape == (M, D // 16) and r.bound.shape == (M,)
+        _check_stream(r, tag=(D, M))
+        big = torch.full((M, D + 48), float("nan"), device=cuda)
+        big[:, 16:16 + D] = x
+        rs = ops.residual_start(big[:, 16:16 + D])                          # ldx = D + 48
+        assert torch.equal(rs.img, r.img) and torch.equal(rs.exp, r.exp) and torch.equal(rs.bound, r.bound)
+        assert torch.equal(rs.ssq, r.ssq)
+    if D >= 4:
+        assert (r.ssq[1] == 0).all() and r.bound[1] == 0
+
+
+def _rms64(x, ln, eps):
+    x = x.double()
+    return x * torch.rsqrt(x.pow(2).mean(1, keepdim=True) + eps) * ln.double()
+
+
+@pytest.mark.parametrize("N", [768, 2304, 3072])
+def test_linear_normed_against_float64(cuda, N):
+    """act(rmsnorm(x) (W (.) w_ln)^T + b) from the stream's image and block sums: f32 and image outputs, 7 / 300 / 5000 rows (the
+    latency kernels and the tile stream) against float64 rmsnorm(x) W^T."""
+    K, eps = 768, 1e-6
+    g = torch.Generator(device=cuda).manual_seed(N)
+    ln = torch.exp(0.5 * torch.randn((K,), device=cuda, generator=g))
+    ln[[5, 77, 600]] = torch.tensor([12.0, 25.0, 30.0], device=cuda)
+    w = torch.randn((N, K), device=cuda, generator=g) * K ** -0.5
+    b = torch.randn((N,), device=cuda, generator=g) * 0.1
+    ws = ops.weight_split(ops.fold_weight(w, ln))
+    for M in (7, 300, 5000):
+        x = _stream_rows(M, K, g, extremes=False)
+        x[1] = 0                                                           # rmsnorm of a zero row: 0 (eps)
+        r = ops.residual_start(x)
+        h64 = _rms64(x, ln, eps)
+        ref, den = h64 @ w.double().T, h64.abs() @ w.double().abs().T
+        got = ops.linear_normed(r, ws, eps)
+        assert torch.isfinite(got).all() and (got[1] == 0).all()
+        err = ((got.double() - ref).abs() / den.clamp_min(1e-30)).max().item()
+        assert err <= TOL, (M, N, err)
+        hs = ops.linear_normed(r, ws, eps, bias=b, relu=True, for_gemm=True)
+        refb = torch.relu(ref + b.double())
+        hv = _image_value(hs)
+        binade = torch.exp2(15 - hs.exp.double())[:, None]
+        assert ((hv - refb).abs() <= TOL * (den + b.double().abs()) + 2.0 ** -21 * binade).all(), (M, N)
+        assert (hs.norm.double() >= torch.linalg.vector_norm(refb, dim=1) * (1 - 1e-5)).all()
+        if M == 300:                                                         # the bar is not loose: an unnormed product misses it
+            assert ((ops.linear(ops.split_rows(x), ws).double() - ref).abs() / den.clamp_min(1e-30)).max() > 1e-3
+
+
+def _residual_case(cuda, N, K, M, seed):
+    g = torch.Generator(device=cuda).manual_seed(seed)
+    x = _stream_rows(M, N, g, extremes=False)
+    a = torch.relu(torch.randn((M, K), device=cuda, generator=g)) * torch.exp(torch.randn((M, 1), device=cuda, generator=g))
+    w = torch.randn((N, K), device=cuda, generator=g) * K ** -0.5
+    w[[3, 100]] *= 60                                                      # rows that write the outlier channels
+    return x, a, w
+
+
+@pytest.mark.parametrize("N,K", [(768, 768), (768, 3072), (1024, 768), (1024, 3072)])
+def test_linear_residual_against_float64(cuda, N, K):
+    """x + a W^T as ResidualRows, a with per-row norms and with one norm_max for all rows, and (K == N) the one-position decoder's
+    x + rmsnorm(x) W^T (normed_eps): x against float64, the image against x, bound >= max |x|, ssq against float64 of the returned
+    x -- on a 70 000-row batch; rows 1, 7, 33, 300, 5000 (from its head and its middle) have the same bits alone."""
+    M, eps = 70000, 1e-6
+    x, a, w = _residual_case(cuda, N, K, M, seed=N + K)
+    r = ops.residual_start(x)
+    ws = ops.weight_split(w)
+    a_s = ops.split_rows(a)
+    a_c = ops.SplitRows(a_s.img, a_s.exp, K, None, float(a_s.norm.max()) * 1.0001)
+    forms = {"rows": (a_s, None), "norm_max": (a_c, None)}
+    ref_of = {"rows": lambda: x.double() + a.double() @ w.double().T}
+    den_of = {"rows": lambda: x.double().abs() + a.double().abs() @ w.double().abs().T}
+    ref_of["norm_max"], den_of["norm_max"] = ref_of["rows"], den_of["rows"]
+    if K == N:
+        ln = torch.exp(0.5 * torch.randn((N,), device=cuda))
+        wf = ops.weight_split(ops.fold_weight(w, ln))
+        forms["normed"] = (r, wf)
+        ref_of["normed"] = lambda: x.double() + _rms64(x, ln, eps) @ w.double().T
+        den_of["normed"] = lambda: x.double().abs() + _rms64(x, ln, eps).abs() @ w.double().abs().T
+    for name, (opnd, wf) in forms.items():
+        wgt = ws if wf is None else wf
+        kw = dict(normed_eps=eps) if name == "normed" else {}
+        out = ops.linear_residual(opnd, wgt, r, **kw)
+        err = ((out.x.double() - ref_of[name]()).abs() / den_of[name]().clamp_min(1e-30)).max().item()
+        assert err <= TOL, (name, N, K, err)
+        _check_stream(out, tag=(name, N, K))
+        for lo, m in ((0, 1), (0, 7), (0, 33), (0, 300), (0, 5000), (33333, 300), (41111, 5000)):
+            rm = ops.ResidualRows(r.x[lo:lo + m], r.img[lo:lo + m], r.exp[lo:lo + m], r.bound[lo:lo + m], r.ssq[lo:lo + m])
+            om = rm if name == "normed" else opnd[lo:lo + m]
+            sub = ops.linear_residual(om, wgt, rm, **kw)
+            for f in ("x", "img", "exp", "bound", "ssq"):
+                assert torch.equal(getattr(sub, f), getattr(out, f)[lo:lo + m]), (name, lo, m, f)
+
+
+def test_folded_stream_through_24_sub_layers(cuda, record_property):
+    """12 blocks of t5-base shape on the folded stream, alternating linear_normed and linear_residual: q|k|v-like
+    projection -> (its v third as the context) -> o, then relu(wi) as an image -> wo.  The carried bound grows by ||a|| wnorm_max
+    at every add and is never re-measured: its drift above the true max |x| is recorded (binades), it never falls below, and
+    the final stream is within the per-sub-layer bar of a float64 run of the same chain (each GEMM's error 2e-6 sum |a||w| of
+    its own inputs, accumulated: the reference is fed the HIP stream's inputs at every sub-layer, so the bar checks each step
+    at the end of a deep chain, where the image is coarsest)."""
+    D, FFW, M, eps = 768, 3072, 512, 1e-6
+    g = torch.Generator(device=cuda).manual_seed(24)
+    x = _stream_rows(M, D, g, extremes=False)
+    x[1] = 0
+    r = ops.residual_start(x)
+    drift, errs = [], []
+    for l in range(12):
+        ln0, ln1 = [torch.exp(0.5 * torch.randn((D,), device=cuda, generator=g)) for _ in range(2)]
+        ln0[l * 7] = ln1[l * 11 + 1] = 20.0
+        wv = torch.randn((D, D), device=cuda, generator=g) * D ** -0.5
+        wo = torch.randn((D, D), device=cuda, generator=g) * D ** -0.5
+        wi = torch.randn((FFW, D), device=cuda, generator=g) * D ** -0.5
+        w2 = torch.randn((D, FFW), device=cuda, generator=g) * FFW ** -0.5
+        wo[[3, 100]] *= 60
+        w2[[401, 700]] *= 60
+        for wn, ln, wout, relu in ((wv, ln0, wo, False), (wi, ln1, w2, True)):
+            x64 = r.x.double()
+            h64 = _rms64(r.x, ln, eps) @ wn.double().T
+            dh = _rms64(r.x, ln, eps).abs() @ wn.double().abs().T
+            if relu:
+                h64 = torch.relu(h64)
+                h = ops.linear_normed(r, ops.weight_split(ops.fold_weight(wn, ln)), eps, relu=True, for_gemm=True)
+                hv = _image_value(h)
+            else:
+                hf = ops.linear_normed(r, ops.weight_split(ops.fold_weight(wn, ln)), eps)
+                h, hv = ops.split_rows(hf), hf.double()
+            assert ((hv - h64).abs() <= 2 * TOL * dh + 2.0 ** -21 * hv.abs().amax(1, keepdim=True)).all(), l
+            r = ops.linear_residual(h, ops.weight_split(wout), r)
+            ref = x64 + hv @ wout.double().T
+            den = x64.abs() + hv.abs() @ wout.double().abs().T
+            errs.append(((r.x.double() - ref).abs() / den.clamp_min(1e-30)).max().item())
+            assert errs[-1] <= TOL, (l, relu, errs[-1])
+            _check_stream(r, tag=(l, relu))
+            live = r.x.abs().amax(1) > 0
+            drift.append(torch.log2(r.bound[live].double() / r.x[live].abs().amax(1).double()).max().item())
+    record_property("bound_drift_binades", drift)
+    record_property("sub_layer_errors", errs)
+    print("bound drift (binades) per sub-layer:", [round(d, 2) for d in drift])
+    assert min(drift) >= 0

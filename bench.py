@@ -6,8 +6,13 @@ Workload (BASELINE.json configs[1], "C2"): the dense arm of MEVI, i.e. what
 against the 8,841,823 x 768 f32 passage-embedding matrix (27.16 GB, resident in
 HBM), exact inner-product top-1000.  One "step" = one full search of all queries.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]       (N > 1: starts its own N ranks)
-  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     (the driver's launch line)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: starts its own N ranks)
+  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...         (launch line with one process per rank)
+
+A plain run does only what the headline needs: generate the data, build the index, warm up, time the K steps, write the
+--dump-outputs lists, print the line.  --full adds every untimed leg after the timed steps, as before: N = 1 the CPU
+baseline, the seq2seq / chain / index-build extras with their certificates and the recorded PMC traffic of the filter;
+N > 1 the per-phase search (`multi_gpu`) and the C5 chain.
 
 Plain `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself -- a CHILD
 `python -m torch.distributed.run` on a free 127.0.0.1 port, before this process has touched the GPU, as the reference's
@@ -388,7 +393,7 @@ def _passage_leg(out, device, n_docs):
 
 
 def extras(device, docs, nq, n_docs, search_ms, index_build_s, with_cpu, query=None, dense_index=None):
-    """Untimed extras (N = 1), measured after the timed region and not part of `value`: the path around the dense search at
+    """Untimed extras (N = 1, --full), measured after the timed region and not part of `value`: the path around the dense search at
     t5-base shapes (synthetic weights, MS MARCO-like query lengths, tools/synth.py) --
       * dense_small_batch: the reference's own profile() regime (batch 1..64), HBM roofline of the f16 image,
       * query tower and NCI generate alone, with the arm's roofline entries (GEMM kernel, per-query FLOP budget),
@@ -796,9 +801,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--docs", type=int, default=N_DOCS, help="corpus rows (default: MSMARCO 8,841,823)")
     ap.add_argument("--queries", type=int, default=N_QUERIES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-seq2seq-legs", action="store_true", help="skip the untimed tower / beam-search extras")
-    ap.add_argument("--chain-limit-s", type=float, default=420.0, help="N > 1: watchdog of the untimed C5 chain leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed legs (CPU baseline, extras, recorded PMC traffic; "
+                         "N > 1: the per-phase search and the C5 chain)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-seq2seq-legs", action="store_true", help="with --full: skip the untimed tower / beam-search extras")
+    ap.add_argument("--chain-limit-s", type=float, default=420.0, help="N > 1 with --full: watchdog of the untimed C5 chain leg")
     ap.add_argument("--exact-f32-path", action="store_true",
                     help="search with the f32-MFMA kernel only (no f16 pre-filter); same results")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -871,9 +879,9 @@ def main():
         elapsed = float(tmax.item())
 
     # N > 1, untimed: one more search with a device synchronisation after every phase, so that a sub-linear point of the
-    # scaling curve can be attributed (local search vs all-gather vs merge vs second round) without another round
+    # scaling curve can be attributed (local search vs all-gather vs merge vs second round) without another round (--full)
     multi_gpu = None
-    if world > 1:
+    if world > 1 and args.full:
         barrier()
         tr = dense.SearchTrace(timed=True)
         step(tr)
@@ -911,13 +919,14 @@ def main():
             kernel, peak = ("ip_filter_h16_kernel" if h16 else "ip_filter_h1_kernel"), PEAK_F16_MFMA_TFLOPS
             peak_note = "f16 MFMA dense peak"
         # HBM-side bytes per filter launch: PMC (FETCH_SIZE x 2 on gfx950) of THIS command, recorded by
-        # tools/prof_traffic.sh + tools/traffic_summary.py; PMC passes cannot run inside the timed bench.
-        traffic, traffic_note, traffic_current = None, "PMC not collected for this configuration", None
+        # tools/prof_traffic.sh + tools/traffic_summary.py; PMC passes cannot run inside the timed bench.  Reported by --full.
+        traffic, traffic_current = None, None
+        traffic_note = "PMC not collected for this configuration" if args.full else "recorded PMC traffic: reported by --full"
         import glob
 
         tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_filter_h1_traffic.json")))
         tfile = tfiles[-1] if tfiles else ""
-        if (not args.exact_f32_path and world == 1 and n_docs == N_DOCS and nq == N_QUERIES and os.path.exists(tfile)):
+        if (args.full and not args.exact_f32_path and world == 1 and n_docs == N_DOCS and nq == N_QUERIES and os.path.exists(tfile)):
             with open(tfile) as f:
                 tj = json.load(f)
             traffic = tj["hbm_side_bytes_per_launch"]
@@ -975,12 +984,12 @@ def main():
         }
         if multi_gpu is not None:
             out["multi_gpu"] = multi_gpu
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(n_docs, nq)
             except Exception as e:
                 out["cpu_baseline_error"] = f"{type(e).__name__}: {e}"
-        if not args.no_seq2seq_legs and world == 1:
+        if args.full and not args.no_seq2seq_legs and world == 1:
             try:
                 out.update(extras(device, docs, nq, n_docs, ms_per_step, index_build_s, with_cpu=not args.no_cpu_baseline,
                                   query=query, dense_index=None if args.exact_f32_path else index))
@@ -991,8 +1000,8 @@ def main():
     else:
         out = None
 
-    # ---- N > 1: the C5 chain on every rank (untimed extra; `value` stays the sharded dense search) ---------------------------
-    if world > 1 and not args.no_seq2seq_legs:
+    # ---- N > 1, --full: the C5 chain on every rank (untimed extra; `value` stays the sharded dense search) --------------------
+    if world > 1 and args.full and not args.no_seq2seq_legs:
         import threading
 
         printed = threading.Event()

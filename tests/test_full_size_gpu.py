@@ -103,7 +103,7 @@ def _bench_two_ranks(backend_env, extra=("--docs", "700000", "--queries", "600",
     env = dict(os.environ, PYTHONPATH=root, MEVI_BENCH_DETAIL=detail, **backend_env)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", *extra],
+                        "--warmup", "1", "--full", *extra],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -171,7 +171,7 @@ def test_bench_starts_its_own_ranks_from_the_plain_command():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PYTHONPATH=root, MEVI_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--docs", "300000", "--queries", "101", "--no-cpu-baseline"],
+                        "--docs", "300000", "--queries", "101", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -216,6 +216,32 @@ def test_bench_dump_outputs_are_the_exact_lists(cuda, tmp_path):
     assert np.array_equal(np.load(out / "query_rows.npy"), np.arange(nq))
     assert np.array_equal(np.load(out / "ids.npy").astype(np.int64), ei)
     assert np.array_equal(np.load(out / "scores.npy").view(np.uint32), es.view(np.uint32))
+
+
+def test_plain_bench_run_carries_the_headline_only(tmp_path):
+    """Without --full the bench times its steps and prints the headline line, nothing else: no CPU baseline, no seq2seq /
+    chain / index-build extras, no recorded PMC traffic."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root, MEVI_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--docs", "100000",
+                        "--queries", "300"], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["config"]["planted_top1_ok"] == 1.0
+    legs = {"cpu_baseline", "cpu_baseline_error", "extras_error", "gemm_mode", "dense_small_batch", "mrr10_match", "seq2seq_arm",
+            "chain_c4", "index_build", "cli_chain", "multi_gpu", "chain_c5"}
+    assert not legs & set(line), sorted(legs & set(line))
+    assert "chain_c4" not in line["config"] and "mrr10_match" not in line["config"]
+    assert line["roofline"]["traffic"] is None and line["roofline"]["launches"] > 0
 
 
 def test_bench_over_rccl_when_two_gpus_are_visible():

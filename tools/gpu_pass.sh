@@ -4,7 +4,7 @@
 # Every step writes under gpurun_out/<tag>/ and prints a few summary lines.  Steps (arguments after a colon, comma separated):
 #   suite[:pytest args]     pytest tests -m gpu -q  (default: whole GPU suite)
 #   smoke                   __graft_entry__.smoke()
-#   bench[:steps,warmup]    bench.py as the driver runs it (default 20,5) + a short summary of the line
+#   bench[:steps,warmup]    bench.py --full (default 20,5: every untimed leg) + a short summary of the line
 #   stats:<name>:<script and args with '+' for spaces>     rocprofv3 --kernel-trace --stats of tools/<script> (kernel_stats csv kept)
 #   tail:<name>:<script+args>   kernel trace of tools/<script> summarised over its timed pass only (tools/trace_tail.py)
 #   stats_bench             the same of `bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-seq2seq-legs`
@@ -30,7 +30,7 @@ while [ $# -gt 0 ]; do
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2;;
     bench)
       st=${rest%%,*}; wu=${rest#*,}; [ -z "$rest" ] && st=20 && wu=5
-      MEVI_BENCH_DETAIL=$O/bench_detail.json timeout 1200 python bench.py --steps $st --warmup $wu > $O/bench.json 2> $O/bench.err
+      MEVI_BENCH_DETAIL=$O/bench_detail.json timeout 1200 python bench.py --steps $st --warmup $wu --full > $O/bench.json 2> $O/bench.err
       echo "bench rc=$? bytes=$(wc -c < $O/bench.json)"; python3 tools/bench_summary.py $O/bench.json;;
     stats)
       name=${rest%%:*}; cmd=$(plus "${rest#*:}"); OUT=$O/stats_$name; rm -rf $OUT; mkdir -p $OUT

@@ -167,6 +167,23 @@ int mevi_rq_encode_fast_stats(const void *workspace, int64_t n, int64_t dim, int
                               void *stream);
 
 /* ------------------------------------------------------------------------
+ * Product-quantisation encode: codes[n, M] (int32, values in [0, K)).
+ * Replaces pq.get_pq_document_cluster / the index path of forward with pq_type 'pq',
+ * dist_mode 'l2' (MEVI/pq.py:249-274, 124-131).
+ *   x f32 [n, dim], codebook f32 [M, K, dsub] (the pq Parameter, pq.py:49-53)
+ *   per subspace j: code = argmin_c sum_k (x[j*dsub + k] - C[j][c][k])^2 (sequential
+ *   fmaf chain over k ascending, lowest index on ties, code 0 for a NaN slice);
+ *   no residual; columns past M*dsub are ignored.  Bit-identical to mevi_rq_encode_f32
+ *   run with one level on each column slice.
+ *   Requirements: M*dsub <= dim (else MEVI_ERR_INVALID_ARG); M <= 32, K <= 256,
+ *   dsub % 4 == 0, dim % 4 == 0 (else MEVI_ERR_UNSUPPORTED, checked before anything
+ *   else, also for n = 0); 16-byte aligned x/codebook.
+ * One launch, every row read once.  Fully stream-ordered; no workspace.
+ * ---------------------------------------------------------------------- */
+int mevi_pq_encode_f32(const float *x, int64_t n, int64_t dim, const float *codebook, int64_t M, int64_t K,
+                       int64_t dsub, int32_t *codes, void *stream);
+
+/* ------------------------------------------------------------------------
  * Linear layer:  C[M,N] = act(A[M,K] . W[N,K]^T + bias[N]) + residual[M,N]
  * Replaces every torch.nn.Linear / torch.matmul of the T5 stacks on the hot path:
  * q/k/v/o and wi/wo (MEVI/transformers/modeling_t5.py:181-186, 217-220, 350-358, 412),

@@ -2,7 +2,7 @@
 """`python main.py --mode eval ...` -- the argv surface of the reference's MEVI/main.py for the eval
 path that marco_eval_nci_rq.sh drives (MEVI/main.py:356-794, 267-337).  Every flag of that script is
 accepted; the ones that configure training are parsed and ignored.  Only --mode eval with
---codebook 1 --pq_type rq --document_encoder ance|cocondenser|ar2 --query_encoder twin|nci --recall_level both|coarse|fine is built
+--codebook 1 --pq_type rq|pq --document_encoder ance|cocondenser|ar2 --query_encoder twin|nci --recall_level both|coarse|fine is built
 (+ the brute-force ablation --eval_all_documents 1 --recall_level fine --knn_topk_by_step 1)
 (the configuration of every shipped eval script); anything else raises.
 
@@ -165,10 +165,13 @@ EVAL_AFFECTING = {
 }
 
 
+PQ_TYPES = ("rq", "pq")     # cluster codings built: residual and product quantisation (l2)
+
+
 def check_supported(a):
     if a.mode == "train" and a.only_gen_rq:   # marco_generate_embedding_n_rq.sh: embeddings + RQ codebook + clusters, then exit
-        if a.document_encoder not in ("ance", "cocondenser", "ar2") or a.pq_type != "rq" or not a.codebook:
-            raise SystemExit("main.py --only_gen_rq 1: needs --codebook 1 --pq_type rq --document_encoder ance|cocondenser|ar2")
+        if a.document_encoder not in ("ance", "cocondenser", "ar2") or a.pq_type not in PQ_TYPES or not a.codebook:
+            raise SystemExit("main.py --only_gen_rq 1: needs --codebook 1 --pq_type rq|pq --document_encoder ance|cocondenser|ar2")
         for k in ("pq_path", "pq_cluster_path", "embedding_path", "document_path", "ckpt_dir"):
             if getattr(a, k) is None:
                 raise SystemExit(f"main.py --only_gen_rq 1: --{k} is required")
@@ -182,7 +185,9 @@ def check_supported(a):
         raise SystemExit(f"main.py --mode eval: --test_set {a.test_set!r} is not built (only 'dev')")
     if a.dataset not in ("marco", "nq_dpr"):
         raise SystemExit(f"main.py --mode eval: --dataset {a.dataset!r} is not built (marco, nq_dpr)")
-    need = dict(codebook=1, pq_type="rq")
+    if a.pq_type not in PQ_TYPES:   # opq: its rotation only comes from a faiss index file (MEVI/pq.py:145-151)
+        raise SystemExit(f"main.py --mode eval: --pq_type {a.pq_type!r} is not built (rq | pq)")
+    need = dict(codebook=1)
     if a.query_encoder == "nci":
         check_nci_query_encoder(a)
     elif a.query_encoder != "twin":

@@ -379,7 +379,7 @@ class EvalRun:
             self.emb = upload_rows(emb, self.dev)
         mark("corpus embeddings file -> HBM (rest after the overlap with the model loads)" if emb_job is not None else "corpus embeddings file -> HBM")
         # RQ codebook + cluster index (pickles if present, else encode on the GPU and write them)
-        self.pq = ProductQuantization("rq", self.M, a.subvector_bits, "l2", d_model, device=self.dev)
+        self.pq = ProductQuantization(getattr(a, "pq_type", "rq"), self.M, a.subvector_bits, "l2", d_model, device=self.dev)
         if ckpt_codebook is not None:             # --infer_ckpt carries pq.codebook: pq.initialize is skipped (main_models.py:4252)
             self.pq.load_codebook(ckpt_codebook)
         else:
@@ -457,6 +457,9 @@ class EvalRun:
         if self.topic:
             assert self.C == 1 or not self.eval_all, "use_topic_model over multi-cluster documents is built for the cluster path"
             self.ratio = float(getattr(a, "topic_score_ratio", 0) or 0)
+            if self.ratio and self.pq.pq_type == "pq" and d_model % self.M:
+                raise NotImplementedError(f"--topic_score_ratio > 0 with --pq_type pq needs dim % subvector_num == 0 (dim "
+                                          f"{d_model}, M {self.M}): the reconstruct vector is M * (dim // M) wide")
             self.doc_path = None
             # topic_score_ratio > 0 (`additional_reconstruct`, main_models.py:1270): doc_proba[d] = <reconstruct(codes(d)), emb[d]>
             # (gen_all_reconstruct :3272-3307 + gen_doc2index_mapping :3360-3364, bmm form of compute_similarity); with
@@ -523,7 +526,8 @@ class EvalRun:
         return results
 
     def _doc_proba(self, chunk=1 << 20):
-        """<sum_j codebook[j][code_j(d)] (level 0 first), emb[d]> for every document, f32 [N] (exact fmaf chains)."""
+        """<reconstruct(code(d)), emb[d]> for every document, f32 [N] (exact fmaf chains over the full dim); the
+        reconstruct vector is sum_j codebook[j][code_j(d)] (level 0 first) for 'rq', the concatenation for 'pq'."""
         from . import ops
 
         N = self.emb.shape[0]
@@ -532,9 +536,12 @@ class EvalRun:
         out = torch.empty(N, dtype=torch.float32, device=self.dev)
         for a in range(0, N, chunk):
             c = codes[a:a + chunk]
-            rec = cb[0][c[:, 0]]
-            for j in range(1, self.M):
-                rec = rec + cb[j][c[:, j]]
+            if self.pq.pq_type == "pq":
+                rec = self.pq.get_reconstruct_vector(c)
+            else:
+                rec = cb[0][c[:, 0]]
+                for j in range(1, self.M):
+                    rec = rec + cb[j][c[:, j]]
             idx = torch.arange(c.shape[0], dtype=torch.int64, device=self.dev)
             out[a:a + chunk] = ops.pair_dot(rec.contiguous(), idx, self.emb[a:a + chunk], idx)
         return out

@@ -53,6 +53,7 @@ _SIGNATURES = {
     "mevi_rq_encode_fast_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
                                         c_void_p]),
     "mevi_rq_encode_fast_stats": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "mevi_pq_encode_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "mevi_gemm_nt_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                  c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mevi_split_kp": (c_int64, [c_int64]),

@@ -5,10 +5,11 @@ from the reference.  Mirrors on_validation_epoch_start of the re
 
   1. gen_doc_embedding (:3077-3180)   docemb.bin, unless it exists: every rank encodes rows // nrank passages (the last
                                       rank takes the rest) into `<prefix>_<rank>.bin`, rank 0 concatenates
-  2. pq.initialize (pq.py:440-486)    rqcodebook*.pt, unless it exists: residual k-means on the embeddings (rank 0)
+  2. pq.initialize (pq.py:440-486)    rqcodebook*.pt, unless it exists: k-means on the embeddings (rank 0) -- per residual
+                                      level (--pq_type rq) or per column slice (--pq_type pq)
   3. gen_pq_doc_cluster (:3182-3220)  rqclus*.pkl / rqmapping*.pkl, unless they exist
 
-Host side only: the device work is TwinTower / BertTower, mevi_amd.rq (k-means, RQ encode)."""
+Host side only: the device work is TwinTower / BertTower, mevi_amd.rq (k-means, RQ / PQ encode)."""
 import os
 import pickle
 
@@ -111,17 +112,19 @@ def build_index(args, rank=0, nrank=1, barrier=None, device=None, tower=None, to
         del tower
     else:
         dim = None
+    pq_type = getattr(args, "pq_type", "rq")
     pq_file = args.pq_path if args.pq_path and os.path.isfile(args.pq_path) else None
     if dim is None:
-        if pq_file is not None:
-            dim = int(torch.load(pq_file, map_location="cpu").shape[-1])
+        if pq_file is not None:   # rq: [M, K, dim]; pq: [M, K, dim // M]
+            shape = torch.load(pq_file, map_location="cpu").shape
+            dim = int(shape[-1]) * (int(shape[0]) if pq_type == "pq" else 1)
         else:
             tower = tower or load_tower(args, device)
             dim = tower.dim
             del tower
     n_docs = os.path.getsize(args.embedding_path) // (4 * dim)
     emb = np.memmap(args.embedding_path, dtype=np.float32, mode="r", shape=(n_docs, dim))
-    pq = ProductQuantization("rq", args.subvector_num, args.subvector_bits, "l2", dim, device=device)
+    pq = ProductQuantization(pq_type, args.subvector_num, args.subvector_bits, "l2", dim, device=device)
     need_clusters = not (os.path.exists(args.pq_cluster_path) and os.path.exists(map_path))
     doc_emb = None
     if rank == 0 and (pq_file is None or need_clusters):

@@ -1,6 +1,6 @@
-"""Residual quantisation on MI355X: the 'rq' / 'l2' slice of the reference's
-`ProductQuantization` (MEVI/pq.py:15) that the eval scripts use, plus the cluster index
-the fine stage consumes.
+"""Residual and product quantisation on MI355X: the 'rq' / 'l2' slice of the reference's
+`ProductQuantization` (MEVI/pq.py:15) that the eval scripts use, its 'pq' / 'l2' slice (the reference's default
+pq_type), plus the cluster index the fine stage consumes.
 
 Reference surface mirrored (same names and argument meaning):
   ProductQuantization(pq_type, subvector_num, subvector_bits, dist_mode, emb_size, ...)
@@ -10,7 +10,9 @@ Reference surface mirrored (same names and argument meaning):
     .get_document_cluster(doc_embeddings, rank, nrank, batch_size, return_mapping)  pq.py:217-247
     .forward(vecs) -> index   (forward_rq, pq.py:337-369; proba/loss are training outputs)
     .get_reconstruct_vector(index)                            pq.py:768-784
-Training (EMA / k-means / gumbel), 'pq' / 'opq' and 'ip' / 'iptol2' are out of scope.
+'pq' differs from 'rq' only in the coding: subspace j of a row (columns j*dsub .. (j+1)*dsub - 1, dsub = dim // M) is
+coded against C[j] alone, reconstruct = concatenation.  EMA / gumbel training, 'opq' and 'ip' / 'iptol2' are out of
+scope.
 """
 from collections import defaultdict
 
@@ -75,6 +77,24 @@ def rq_encode(x, codebook, mode=None):
             st = L.mevi_rq_encode_f32(hip.ptr(x), n, dim, hip.ptr(codebook), M, K, hip.ptr(codes), hip.stream_ptr())
             hip.check(st, "mevi_rq_encode_f32")
             _LAST_ENCODE.update(path="exact", n=n, dim=dim, M=M, K=K)
+    return codes
+
+
+def pq_encode(x, codebook):
+    """codes i32[n, M] of x f32[n, dim] against a product codebook f32[M, K, dsub] (CUDA tensors): code j = the nearest
+    centroid of C[j] to x[:, j*dsub:(j+1)*dsub] (csrc/pq_encode.hip; the oracle's arithmetic bit for bit)."""
+    hip.require_gpu()
+    assert x.is_cuda and codebook.is_cuda and x.dtype == torch.float32 and codebook.dtype == torch.float32
+    x = x.contiguous()
+    codebook = codebook.contiguous()
+    M, K, dsub = codebook.shape
+    assert x.dim() == 2 and M * dsub <= x.shape[1], (x.shape, codebook.shape)
+    n, dim = x.shape
+    codes = torch.empty((n, M), dtype=torch.int32, device=x.device)
+    with hip.device_guard(x.device):
+        st = hip.lib().mevi_pq_encode_f32(hip.ptr(x), n, dim, hip.ptr(codebook), M, K, dsub, hip.ptr(codes),
+                                          hip.stream_ptr())
+    hip.check(st, "mevi_pq_encode_f32")
     return codes
 
 
@@ -185,6 +205,19 @@ def train_rq_codebook(x, M, K, seed=0, **kw):
     return torch.stack(book), torch.stack(codes, 1).contiguous()
 
 
+def train_pq_codebook(x, M, K, seed=0, **kw):
+    """Product quantisation codebook as the reference trains it (MEVI/pq.py:577-587): subspace j is k-means on the column
+    slice j*dsub .. (j+1)*dsub - 1 (dsub = dim // M), seeded seed + j.  Returns (codebook f32[M, K, dsub], codes i32[n, M])."""
+    x = x.contiguous()
+    dsub = x.shape[1] // M
+    book, codes = [], []
+    for j in range(M):
+        centers, labels, _ = kmeans(x[:, j * dsub:(j + 1) * dsub].contiguous(), K, seed=seed + j, **kw)
+        book.append(centers)
+        codes.append(labels)
+    return torch.stack(book), torch.stack(codes, 1).contiguous()
+
+
 class ClusterIndex:
     """CSR form of the reference's `pq_doc_cluster: dict[tuple -> list[int]]` and
     `pq_mapping: dict[int -> tuple]` (MEVI/main_models.py:3200-3220).
@@ -276,15 +309,16 @@ class ClusterIndex:
 class ProductQuantization:
     def __init__(self, pq_type="rq", subvector_num=4, subvector_bits=5, dist_mode="l2", emb_size=768,
                  pq_init_method="kmeans", pq_update_method="none", device=None, **unused):
-        if pq_type != "rq" or dist_mode != "l2":
-            raise NotImplementedError("only pq_type='rq', dist_mode='l2' is on the MEVI eval path")
+        if pq_type not in ("rq", "pq") or dist_mode != "l2":
+            raise NotImplementedError("only pq_type 'rq' or 'pq' with dist_mode='l2' is on the MEVI eval path")
         self.pq_type, self.dist_mode = pq_type, dist_mode
         self.subvector_num, self.subvector_bits = subvector_num, subvector_bits
         self.subvector_cents = 2 ** subvector_bits
-        self.emb_size = self.last_dim = emb_size
+        self.emb_size = emb_size
+        self.last_dim = emb_size if pq_type == "rq" else emb_size // subvector_num     # pq.py:49-53
         self.pq_init_method = pq_init_method
         self.device = torch.device(device if device is not None else "cuda")
-        self.codebook = torch.empty((subvector_num, self.subvector_cents, emb_size), dtype=torch.float32,
+        self.codebook = torch.empty((subvector_num, self.subvector_cents, self.last_dim), dtype=torch.float32,
                                     device=self.device)
 
     def get_codebook(self):
@@ -299,7 +333,7 @@ class ProductQuantization:
         self.codebook.copy_(t.to(self.device))
 
     def initialize(self, index_file, doc_emb=None, rank=0, seed=0, pq_cluster_path=None, encode_batch_size=None):
-        """Rank 0 loads `rqcodebook{M}_{bits}.pt` (torch.save of the f32[M,K,dim] parameter),
+        """Rank 0 loads `rqcodebook{M}_{bits}.pt` (torch.save of the f32[M,K,dim] parameter; f32[M,K,dim//M] for 'pq'),
         then the codebook is broadcast (RCCL) when a process group exists."""
         import os
 
@@ -314,25 +348,29 @@ class ProductQuantization:
                 if index_file is not None:
                     torch.save(self.codebook.detach().cpu(), index_file)
             else:
-                raise FileNotFoundError(f"RQ codebook {index_file} not found and no embeddings to train one on")
+                raise FileNotFoundError(f"{self.pq_type.upper()} codebook {index_file} not found and no embeddings to train one on")
         if dist.is_available() and dist.is_initialized():
             dist.broadcast(self.codebook, 0)
 
     def unsupervised_update_codebook_manually(self, doc_emb, seed, kmeans_method="kmeans"):
-        """Train the residual codebook on `doc_emb` (MEVI/pq.py:550-598, the scikit-learn path): level i = k-means
-        (k = 2**bits) on the residual of levels < i.  Runs on the GPU (`train_rq_codebook`); sets `last_preds`
-        (i64 ndarray [n, M]) like the reference."""
+        """Train the codebook on `doc_emb` (MEVI/pq.py:550-598, the scikit-learn path): 'rq' level i = k-means
+        (k = 2**bits) on the residual of levels < i, 'pq' subspace j = k-means on column slice j.  Runs on the GPU
+        (`train_rq_codebook` / `train_pq_codebook`); sets `last_preds` (i64 ndarray [n, M]) like the reference."""
         assert kmeans_method == "kmeans", kmeans_method
         print("Updating codebook using KMeans...")
         x = doc_emb if torch.is_tensor(doc_emb) else torch.from_numpy(np.ascontiguousarray(doc_emb, dtype=np.float32))
         x = x.to(self.device, torch.float32)
-        book, codes = train_rq_codebook(x, self.subvector_num, self.subvector_cents, seed=int(seed))
+        train = train_rq_codebook if self.pq_type == "rq" else train_pq_codebook
+        book, codes = train(x, self.subvector_num, self.subvector_cents, seed=int(seed))
         self.codebook.copy_(book)
         self.last_preds = codes.cpu().numpy().astype(np.int64)
 
+    def _encode(self, x):
+        return rq_encode(x, self.codebook) if self.pq_type == "rq" else pq_encode(x, self.codebook)
+
     def forward(self, vecs, return_loss=False):
         """index i32[n, M]; the reference's (proba, index, loss) triple minus the training outputs."""
-        return None, rq_encode(vecs.to(self.device, torch.float32), self.codebook), None
+        return None, self._encode(vecs.to(self.device, torch.float32)), None
 
     def get_document_cluster(self, doc_embeddings, rank, nrank, batch_size=1 << 20, return_mapping=False,
                              as_index=False):
@@ -348,7 +386,7 @@ class ProductQuantization:
             b1 = min(b0 + batch_size, ending)
             chunk = doc_embeddings[b0:b1]
             chunk = chunk if torch.is_tensor(chunk) else torch.from_numpy(np.ascontiguousarray(chunk, dtype=np.float32))
-            parts.append(rq_encode(chunk.to(self.device, torch.float32), self.codebook).cpu())
+            parts.append(self._encode(chunk.to(self.device, torch.float32)).cpu())
         codes = torch.cat(parts).numpy() if parts else np.zeros((0, self.subvector_num), np.int32)
         index = ClusterIndex.from_codes(codes, self.subvector_cents, start=start)
         print("Number of document clusters:", len(index.keys))
@@ -366,7 +404,8 @@ class ProductQuantization:
     @torch.no_grad()
     def beam_search(self, doc_emb, num_return_sequences, num_beams=None, do_sample=False, return_proba=False):
         """Top-R code paths per row (pq.beam_search, MEVI/pq.py:613-713, rq_topk_score='prod'): per level
-        softmax(-distance) times the running beam probability, top-R over beams x K.  Returns labels
+        softmax(-distance) times the running beam probability, top-R over beams x K.  'rq' scores the residual each
+        beam hands down, 'pq' scores column slice j against C[j] (the same row for every beam).  Returns labels
         i32[bs, R, M] (and probabilities f32[bs, R])."""
         assert not do_sample and num_beams in (None, num_return_sequences)
         with hip.device_guard(self.device):          # stream_ptr() and the launches below refer to the codebook's GPU
@@ -374,7 +413,8 @@ class ProductQuantization:
 
     def _beam_search(self, doc_emb, num_return_sequences, return_proba):
         L = hip.lib()
-        R, M, K, dim = num_return_sequences, self.subvector_num, self.subvector_cents, self.emb_size
+        R, M, K, dim = num_return_sequences, self.subvector_num, self.subvector_cents, self.last_dim
+        pq = self.pq_type == "pq"
         x = doc_emb.to(self.device, torch.float32).contiguous()
         bs = x.shape[0]
         resid, nb = x, 1
@@ -382,9 +422,12 @@ class ProductQuantization:
         labels = torch.zeros((bs, 1, 0), dtype=torch.int32, device=self.device)
         base = torch.arange(bs, device=self.device)[:, None]
         for j in range(M):
-            nd = torch.empty((bs * nb, K), dtype=torch.float32, device=self.device)
-            hip.check(L.mevi_rq_neg_dist_f32(hip.ptr(resid), bs * nb, dim, hip.ptr(self.codebook[j]), K, hip.ptr(nd),
-                                             hip.stream_ptr()), "mevi_rq_neg_dist_f32")
+            src_rows = x[:, j * dim:(j + 1) * dim].contiguous() if pq else resid
+            nd = torch.empty((src_rows.shape[0], K), dtype=torch.float32, device=self.device)
+            hip.check(L.mevi_rq_neg_dist_f32(hip.ptr(src_rows), src_rows.shape[0], dim, hip.ptr(self.codebook[j]), K,
+                                             hip.ptr(nd), hip.stream_ptr()), "mevi_rq_neg_dist_f32")
+            if pq and nb > 1:                      # one score row per document, repeated for each of its beams
+                nd = nd[:, None, :].expand(bs, nb, K).reshape(bs * nb, K).contiguous()
             if R < nb * K:
                 sc = torch.empty((bs, R), dtype=torch.float32, device=self.device)
                 parent = torch.empty((bs, R), dtype=torch.int32, device=self.device)
@@ -401,7 +444,7 @@ class ProductQuantization:
                 nb_new = nb * K
             labels = torch.cat([torch.gather(labels, 1, parent.long()[:, :, None].expand(-1, -1, labels.shape[2])),
                                 code[:, :, None]], dim=2)
-            if j != M - 1:
+            if j != M - 1 and not pq:
                 src = (base * nb + parent.long()).reshape(-1).contiguous()
                 nxt = torch.empty((bs * nb_new, dim), dtype=torch.float32, device=self.device)
                 hip.check(L.mevi_gather_sub_f32(hip.ptr(resid), hip.ptr(src), hip.ptr(self.codebook[j]),
@@ -426,8 +469,12 @@ class ProductQuantization:
         return out
 
     def get_reconstruct_vector(self, index, codebook=None):
+        """pq.get_reconstruct_vector (MEVI/pq.py:768-784): 'rq' = sum of the chosen centroids (level 0 first),
+        'pq' = their concatenation (f32 [..., M * dsub])."""
         cb = self.codebook if codebook is None else codebook
         index = index.to(cb.device).long()
+        if self.pq_type == "pq":
+            return torch.cat([cb[j][index[..., j]] for j in range(cb.shape[0])], dim=-1)
         out = torch.zeros(index.shape[:-1] + (cb.shape[-1],), dtype=torch.float32, device=cb.device)
         for j in range(cb.shape[0]):
             out = out + cb[j][index[..., j]]

@@ -428,6 +428,39 @@ int mevi_beam_step_tree_f32(const float *logits, const float *beam_scores, int64
                             int64_t n_nodes, float *out_scores, int32_t *out_parent, int32_t *out_code,
                             int32_t *out_node, void *stream);
 
+/* The beam step under a VARIABLE-DEPTH prefix tree (semantic ids of different lengths, --codebook 0): eos is a candidate
+ * wherever an id ends, so the reference's hypothesis bookkeeping runs per step (MEVI/transformers/generation_utils.py:
+ * 851-945, BeamHypotheses :1268-1315).  Step p (cur_len = p + 1), R beams per query from the first step:
+ *   logits f32 [nq*R, K+1] (col 0 = eos), beam_scores f32 [nq, R], node i32 [nq, R] (level-p node, < 0 or >= n_nodes = off
+ *   the tree: nothing allowed), prefix i32 [nq, R, T] (tokens 0..p of every beam, token 0 = the start token),
+ *   anc i32 [nq*R, p] (rows of the beams' earlier positions; may be null with out_anc null),
+ *   tree_mask u32 [n_nodes, ceil(K/32)], tree_base i32 [n_nodes] as mevi_beam_step_tree_f32, tree_ends u8 [n_nodes]
+ *   (1 = an id ends at the node: eos allowed), len_pow f64 [T+1] (len_pow[l] = l ** length_penalty, made by the host so
+ *   that the division below is the reference's).
+ * cand[r, c] = beam_score[r] + log_softmax(logits[r])[c] where allowed, -inf elsewhere; the 2R best by (score desc,
+ * r*(K+1)+c asc) are walked in rank order: an eos candidate of rank < R enters the pool with score (f64) cand / len_pow[p+1]
+ * (a full pool replaces its worst entry when the new score is strictly better), the first R others become the open beams:
+ * out_scores f32 / out_parent / out_code / out_node i32 [nq, R], out_prefix i32 [nq, R, T] (token p+1 = 2 + p*K + code),
+ * out_anc i32 [nq*R, p+1] (anc of the parent, then the parent's row).  The pool -- pool_score f64 [nq, R], pool_seq /
+ * pool_len i32 [nq, R], pool_tok i32 [nq, R, T], pool_state i32 [nq, 4] = (entries, insertions, done, 0), all zero before
+ * step 0 -- is updated in place; done |= pool full and worst >= best candidate / len_pow[p+1]; a done query's pool is
+ * left alone while its beams keep flowing.  Refused before launch: R > 32, K > 256, T > 64, p + 1 >= T. */
+int mevi_beam_step_var_f32(const float *logits, const float *beam_scores, const int32_t *node, const int32_t *prefix,
+                           const int32_t *anc, int64_t nq, int64_t R, int64_t K, int64_t p, int64_t T,
+                           const uint32_t *tree_mask, const int32_t *tree_base, const uint8_t *tree_ends, int64_t n_nodes,
+                           const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
+                           int32_t *pool_tok, int32_t *pool_state, float *out_scores, int32_t *out_parent,
+                           int32_t *out_code, int32_t *out_node, int32_t *out_prefix, int32_t *out_anc, void *stream);
+
+/* After the last step (generation_utils.py:947-1001): queries that are not done add their R open beams (beam_scores f32
+ * [nq, R], prefix i32 [nq, R, T], length T) to their pools; then every pool is written best first (score descending, equal
+ * scores latest insertion first): decoded i64 [nq*R, T] (the tokens, eos = 1 where it fits, then pad 0), scores f64 [nq*R],
+ * lengths i32 [nq*R] (tokens before eos). */
+int mevi_beam_finalize_var_f32(const float *beam_scores, const int32_t *prefix, int64_t nq, int64_t R, int64_t T,
+                               const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
+                               int32_t *pool_tok, int32_t *pool_state, int64_t *decoded, double *scores, int32_t *lengths,
+                               void *stream);
+
 /* Row-wise (log-)softmax with the beam step's arithmetic (max, sum of expf(x - max), logf), for the branches that keep
  * EVERY candidate instead of a top-R: mode 0 = log_softmax of x f32 [rows, cols] (the all-paths walk `_generate_all`,
  * MEVI/transformers/generation_utils.py:1013-1136); mode 1 = scale[row] * softmax(x) (pq.beam_search while beams * K <= R,

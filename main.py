@@ -3,7 +3,8 @@
 path that marco_eval_nci_rq.sh drives (MEVI/main.py:356-794, 267-337).  Every flag of that script is
 accepted; the ones that configure training are parsed and ignored.  Only --mode eval with
 --codebook 1 --pq_type rq|pq --document_encoder ance|cocondenser|ar2 --query_encoder twin|nci --recall_level both|coarse|fine is built
-(+ the brute-force ablation --eval_all_documents 1 --recall_level fine --knn_topk_by_step 1)
+(+ the brute-force ablation --eval_all_documents 1 --recall_level fine --knn_topk_by_step 1, and --codebook 0 --label_length_cutoff L
+--mapping_path ... --kary K: semantic ids of different lengths over the tower path)
 (the configuration of every shipped eval script); anything else raises.
 
 One process per GPU: `--n_gpu N` spawns N ranks itself like the reference (queries split by rank,
@@ -99,6 +100,13 @@ def parsers_parser(argv=None):
     args.query_embed_accum = given.get("--query_embed_accum", "maxpool")
     if args.query_encoder == "nci":
         ignored = [f for f in ignored if f[0] not in ("--qtower", "--query_embed_accum")]
+    # --codebook 0 (semantic ids): the flags that define the ids, their tree and the clusters (MEVI/main.py:420,559-566,780-787)
+    args.label_length_cutoff = int(given.get("--label_length_cutoff", 0))
+    args.mapping_path = given.get("--mapping_path")
+    args.kary = int(given.get("--kary", 0))
+    args.max_output_length = int(given.get("--max_output_length", 10))
+    if not args.codebook:
+        ignored = [f for f in ignored if f[0] not in ("--label_length_cutoff", "--mapping_path", "--kary", "--max_output_length")]
     args.ignored_flags = ignored
     args.recall_num = sorted(int(r) for r in args.recall_num.split(","))
     if not args.document_encoder or args.recall_level == "coarse":      # MEVI/main.py:750-752
@@ -188,6 +196,8 @@ def check_supported(a):
     if a.pq_type not in PQ_TYPES:   # opq: its rotation only comes from a faiss index file (MEVI/pq.py:145-151)
         raise SystemExit(f"main.py --mode eval: --pq_type {a.pq_type!r} is not built (rq | pq)")
     need = dict(codebook=1)
+    if not a.codebook:
+        return check_semantic_ids(a)
     if a.query_encoder == "nci":
         check_nci_query_encoder(a)
     elif a.query_encoder != "twin":
@@ -209,6 +219,41 @@ def check_supported(a):
     if a.num_return_sequences > (2 ** a.subvector_bits) ** a.subvector_num:
         raise SystemExit("num_return_sequences exceeds the number of code paths (2**subvector_bits)**subvector_num: the "
                          "reference would return -1e9 placeholder hypotheses")
+
+
+def check_semantic_ids(a):
+    """--codebook 0: documents carry semantic ids of different lengths (--mapping_path, `--id_class bert_k30_c30_1`), the
+    decode tree is built from them and their --label_length_cutoff prefixes are the clusters the tower re-ranks
+    (MEVI/main_models.py:823-825,1707-1728,3924-3928).  Built for the tower path; --pq_path / --pq_cluster_path are not read."""
+    what = "main.py --mode eval --codebook 0"
+    if a.query_encoder != "twin":
+        raise SystemExit(f"{what}: --query_encoder {a.query_encoder!r} is not built (only twin)")
+    if a.dataset != "marco":
+        raise SystemExit(f"{what}: --dataset {a.dataset!r} is not built (only marco)")
+    if a.recall_level not in ("both", "coarse", "fine"):
+        raise SystemExit(f"{what}: --recall_level {a.recall_level!r} is not built (both | coarse | fine)")
+    if a.label_length_cutoff <= 0:      # MEVI/main.py:780-781 asserts it for the tower path
+        raise SystemExit(f"{what}: --label_length_cutoff L > 0 is required (the L-code prefixes of the ids are the clusters)")
+    if not a.mapping_path:
+        raise SystemExit(f"{what}: --mapping_path is required (pickle dict: document -> semantic id)")
+    if a.kary <= 0:
+        raise SystemExit(f"{what}: --kary > 0 is required (the codes of one level)")
+    if a.max_output_length < a.label_length_cutoff + 2:
+        raise SystemExit(f"{what}: --max_output_length {a.max_output_length} cuts the beams below --label_length_cutoff "
+                         f"{a.label_length_cutoff} codes: no beam could name a cluster (needs >= cutoff + 2)")
+    for k, v in (("doc_multiclus", 1), ("eval_all_documents", 0), ("use_topic_model", 0), ("knn_topk_by_step", 0)):
+        if getattr(a, k) != v:
+            raise SystemExit(f"{what}: --{k} {getattr(a, k)!r} is not built (only {v!r})")
+    if a.query_embedding_path:
+        raise SystemExit(f"{what}: --query_embedding_path is not built")
+    for k in ("embedding_path", "custom_save_path"):
+        if getattr(a, k) is None:
+            raise SystemExit(f"{what}: --{k} is required")
+    if a.nci_ckpt is None and a.infer_ckpt is None:
+        raise SystemExit(f"{what}: --nci_ckpt or --infer_ckpt is required")
+    if a.num_return_sequences > 32 or a.kary > 256 or a.label_length_cutoff > 7:
+        raise SystemExit(f"{what}: the variable-depth beam search takes --num_return_sequences <= 32, --kary <= 256 and "
+                         "--label_length_cutoff <= 7")
 
 
 QTOWER_PIECES = ("enc", "encmask", "dec", "emb")

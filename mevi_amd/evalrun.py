@@ -292,6 +292,10 @@ class EvalRun:
         self.dev = torch.device(device if device is not None else "cuda")
         a = args
         self.M, self.K, self.R = a.subvector_num, 2 ** a.subvector_bits, a.num_return_sequences
+        # --codebook 0: semantic ids of different lengths; beams carry at most --label_length_cutoff codes of --kary values
+        self.semantic = not getattr(a, "codebook", 1)
+        if self.semantic:
+            self.M, self.K = a.label_length_cutoff, a.kary
         tower_override, ckpt_codebook = {}, None
         # --query_encoder nci: the fine stage pools the NCI model's own states per (query, beam) (T5FineTuner.clus_repr);
         # the query tower is neither loaded nor run
@@ -378,6 +382,47 @@ class EvalRun:
             emb = np.memmap(a.embedding_path, dtype=np.float32, mode="r", shape=(n_docs, d_model))
             self.emb = upload_rows(emb, self.dev)
         mark("corpus embeddings file -> HBM (rest after the overlap with the model loads)" if emb_job is not None else "corpus embeddings file -> HBM")
+        if self.semantic:
+            self._init_semantic_ids(a, n_docs)
+        else:
+            self._init_pq_clusters(a, rank, n_docs, d_model, ckpt_codebook)
+        self.fine = mfine.FineStage(self.emb, self.index)
+        self._init_logs(a, rank, nrank, d_model)
+
+    def _init_semantic_ids(self, a, n_docs):
+        """--codebook 0: the ids of --mapping_path (dict document -> id; an id is a '-'-joined string or a sequence of codes,
+        MEVI/main_models.py:91-95,1432-1434) cut to --label_length_cutoff codes define the decode tree (main_models.py:1707-1728
+        through encode_single_newid's cut), the clusters (`newid[:label_length_cutoff]`, :1868) and the gt codes (:815-825).
+        Clusters live in a ClusterIndex (CSR) over codes shifted by one and padded with 0 to L columns, base K + 1."""
+        from .nci import RaggedPrefixTree
+
+        t0 = time.perf_counter()
+        with open(a.mapping_path, "rb") as f:
+            mapping = pickle.load(f)
+        if sorted(mapping) != list(range(len(mapping))) or len(mapping) != n_docs:
+            raise SystemExit(f"--mapping_path: needs one id per document 0 .. {n_docs - 1} of --embedding_path "
+                             f"({len(mapping)} entries found)")
+        L = self.M
+        codes = np.zeros((n_docs, L), np.int64)                 # code + 1, 0 = beyond the id's end
+        for doc in range(n_docs):
+            newid = mapping[doc]
+            seq = [int(c) for c in (newid.split("-") if isinstance(newid, str) else newid)][:L]
+            codes[doc, :len(seq)] = np.asarray(seq, np.int64) + 1
+        del mapping
+        lengths = (codes > 0).sum(1)
+        if (lengths == 0).any() or (np.cumsum(codes == 0, 1)[codes > 0] > 0).any() or codes.max() > self.K:
+            raise SystemExit("--mapping_path: ids must be non-empty sequences of codes in [0, --kary)")
+        self.sem_codes, self.sem_len = codes, lengths
+        self.sem_tree = RaggedPrefixTree(codes - 1, self.K, self.dev, lengths=lengths, levels=L + 1)
+        self.index = ClusterIndex.from_codes(codes, self.K + 1)
+        if self.R > len(self.index.keys):      # as the codebook path refuses R > K**M: the search would return -inf placeholders
+            raise SystemExit(f"--num_return_sequences {self.R} exceeds the {len(self.index.keys)} distinct ids (cut to "
+                             f"--label_length_cutoff {L}): the reference would return placeholder hypotheses")
+        self.C, self.aggregate, self.pq, self.mapping = 1, None, None, None
+        mark("semantic ids: mapping -> decode tree + cluster index (%.2f s)" % (time.perf_counter() - t0), sync=True)
+        print("Number of all document clusters:", len(self.index.keys))
+
+    def _init_pq_clusters(self, a, rank, n_docs, d_model, ckpt_codebook):
         # RQ codebook + cluster index (pickles if present, else encode on the GPU and write them)
         self.pq = ProductQuantization(getattr(a, "pq_type", "rq"), self.M, a.subvector_bits, "l2", d_model, device=self.dev)
         if ckpt_codebook is not None:             # --infer_ckpt carries pq.codebook: pq.initialize is skipped (main_models.py:4252)
@@ -431,7 +476,8 @@ class EvalRun:
                 with open(multi_path, "wb") as f:
                     pickle.dump(self.index.to_dicts()[0], f)
             self.barrier()
-        self.fine = mfine.FineStage(self.emb, self.index)
+
+    def _init_logs(self, a, rank, nrank, d_model):
         self._dense_index = None
         # --query_embedding_path (this build): the file `generate.py --gen_query` wrote for the same query file.  The
         # reference encodes every query a second time inside infer() (main_models.py:3797-3812); the embeddings are the
@@ -629,11 +675,22 @@ class EvalRun:
         keep = self.nci_query and want_f
         # plain `enc` pools the padded positions too: their states must be the reference's, not the packed encoder's zeros
         pad = keep and bool(self.qpool_mode & ops.QPOOL_PIECES["enc"]) and not self.qpool_mode & ops.QPOOL_PIECES["encmask"]
-        decoded, scores, enc_h, dec_h = self.nci.generate(ids, mask, num_beams=R, num_return_sequences=R,
-                                                          length_penalty=a.length_penalty, max_length=self.M + 2, graph=timing,
-                                                          decode_tree=self.decode_tree(), output_dec_hidden=keep, pad_encoder=pad)
         B = len(texts)
-        codes = decode_token(decoded, self.K).view(B, R, self.M).cpu().numpy()
+        if self.semantic:
+            # beams of different lengths: a beam's cluster is tuple(d[:eos_idx]) (main_models.py:3924-3928) -- here the codes
+            # shifted by one and padded with 0, the key form of the cluster index; the logs get the trimmed lists
+            decoded, scores, enc_h, dec_h, lengths = self.nci.generate(ids, mask, num_beams=R, num_return_sequences=R,
+                                                                       length_penalty=a.length_penalty, max_length=self.M + 2,
+                                                                       graph=timing, decode_tree=self.sem_tree)
+            live = torch.arange(self.M, device=decoded.device)[None, :] < (lengths.long() - 1)[:, None]
+            codes = torch.where(live, decode_token(decoded, self.K) + 1, 0).view(B, R, self.M).cpu().numpy()
+            beam_lists = [[[c - 1 for c in beam if c > 0] for beam in q] for q in codes.tolist()]
+        else:
+            decoded, scores, enc_h, dec_h = self.nci.generate(ids, mask, num_beams=R, num_return_sequences=R,
+                                                              length_penalty=a.length_penalty, max_length=self.M + 2, graph=timing,
+                                                              decode_tree=self.decode_tree(), output_dec_hidden=keep, pad_encoder=pad)
+            codes = decode_token(decoded, self.K).view(B, R, self.M).cpu().numpy()
+            beam_lists = codes.tolist()
         scores = np.array(scores).reshape(B, R)
         if timing:
             t1 = time.time()
@@ -642,7 +699,7 @@ class EvalRun:
             ndoc = self.fine.candidates_device(codes)[3]
             results = []
             for i, text in enumerate(texts):
-                d = codes[i].tolist()
+                d = beam_lists[i]
                 cr, gt_codes = self._coarse_ranks(d, doc_ids[i])
                 self.coarse_log.add((text, d, gt_codes, scores[i].tolist()) if self.nq is None else (text, d, scores[i].tolist()))
                 results.append((text, int(ndoc[i]), cr))
@@ -667,7 +724,7 @@ class EvalRun:
         gt_s = self.fine.gt_scores(qemb, doc_ids) if self.hn_log is not None and nq is None else None
         results = []
         for i, text in enumerate(texts):
-            d = codes[i].tolist()
+            d = beam_lists[i]
             docs, sc = ranked[i]
             if want_c:
                 cr, gt_codes = self._coarse_ranks(d, doc_ids[i])
@@ -699,6 +756,9 @@ class EvalRun:
         if self.nq is not None:   # main_models.py:3738-3757: first beam cluster holding a document that answers the question
             answering = self.nq.docs_answering(gts)
             return [next((j for j, c in enumerate(d) if np.isin(self.index.lookup(c), answering).any()), None)], None
+        if self.semantic:         # the gt ids cut like the beams (main_models.py:815-825)
+            gt_codes = [(self.sem_codes[g, :self.sem_len[g]] - 1).tolist() for g in gts]
+            return tuple(d.index(g) if g in d else None for g in gt_codes), gt_codes
         if self.C > 1:            # use_pq_topk_label (main_models.py:3761-3771): best rank over a gt doc's C paths
             gt_codes = [self.doc_topk[g].tolist() for g in gts]
             return tuple(min((d.index(g) for g in paths if g in d), default=None) for paths in gt_codes), gt_codes

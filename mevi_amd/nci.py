@@ -375,6 +375,83 @@ class PrefixTree:
             self.base.append(torch.from_numpy(child_of_row[first_par].astype(np.int32)).to(device))
 
 
+class RaggedPrefixTree:
+    """The decode tree of semantic ids (--codebook 0): TreeBuilder().add(encode_single_newid(id)) for every document id
+    (MEVI/main_models.py:50-69, 83-108, 1707-1728), ids of DIFFERENT lengths.  Level arrays as PrefixTree -- level p holds
+    the distinct p-code prefixes in lexicographic order, `mask[p]` / `base[p]` the children -- plus `ends[p]` u8 [n_p]: 1
+    where an id ends at the node, i.e. eos is a child there.  A node may both end an id and have children (ids that are
+    prefixes of one another, or cut to the same `cutoff` codes).  Levels 0 .. depth - 1 carry arrays (every level has at
+    least one row so that its pointers exist); nodes of level `depth` are leaves that exist as indices only.
+    `paths`: sequences of codes (or an [n, D] array padded with -1 + `lengths`); `cutoff`: keep the first `cutoff` codes
+    (--label_length_cutoff cuts the tokens to max_output_length - 2).  Built on the host, once per process."""
+
+    _serial = 0
+
+    def __init__(self, paths, K, device, lengths=None, cutoff=None, levels=None):
+        if lengths is None:
+            lengths = np.fromiter((len(x) for x in paths), np.int64, len(paths))
+            D = int(lengths.max()) if len(lengths) else 0
+            arr = np.full((len(paths), max(D, 1)), -1, np.int64)
+            for i, x in enumerate(paths):
+                arr[i, :len(x)] = x
+        else:
+            arr, lengths = np.asarray(paths, np.int64), np.asarray(lengths, np.int64)
+            arr = np.where(np.arange(arr.shape[1])[None, :] < lengths[:, None], arr, -1)
+        assert arr.shape[0] > 0, "no ids"
+        if cutoff is not None:
+            arr, lengths = arr[:, :cutoff], np.minimum(lengths, cutoff)
+        live = np.where(np.arange(arr.shape[1])[None, :] < lengths[:, None], arr, 0)
+        assert live.min() >= 0 and live.max() < K, "codes outside [0, K)"
+        arr = np.unique(arr, axis=0)                       # lexicographic; the pad -1 puts a prefix before its extensions
+        lengths = (arr >= 0).sum(1)
+        n, D = arr.shape[0], int(lengths.max())
+        self.K, self.depth, self.n_paths = K, D, n
+        RaggedPrefixTree._serial += 1
+        self.serial = RaggedPrefixTree._serial             # names the tree in graph-cache keys (an id() can be reused)
+        n_levels = max(D, 1) if levels is None else levels
+        assert n_levels >= D, "tree deeper than the levels asked for"
+        W = (K + 31) // 32
+        self.mask, self.base, self.ends, self.n_nodes = [], [], [], []
+        self._host = []                                    # (mask u32, base, ends) per level, for tools and tests
+
+        def level_nodes(p):                                # node of every row at level p (-1: the id is shorter), node count
+            rows = np.flatnonzero(lengths >= p)
+            node = np.full(n, -1, np.int64)
+            if rows.size == 0:
+                return node, 0, rows, rows
+            first = np.ones(rows.size, bool)
+            if p > 0:
+                first[1:] = (arr[rows[1:], :p] != arr[rows[:-1], :p]).any(1)
+            else:
+                first[1:] = False
+            idx = np.cumsum(first) - 1
+            node[rows] = idx
+            return node, int(idx[-1]) + 1, rows, rows[first]
+
+        node, cnt, rows, firsts = level_nodes(0)
+        for p in range(n_levels):
+            nxt = level_nodes(p + 1)
+            m = max(cnt, 1)
+            mask = np.zeros((m, W), np.uint32)
+            base = np.zeros(m, np.int32)
+            ends = np.zeros(m, np.uint8)
+            if cnt:
+                ends[:cnt] = lengths[firsts] == p          # the id that ends here, if any, is the node's first row
+                ch = nxt[3]                                # first row of every child node, in (parent, code) order
+                if ch.size:
+                    par, code = node[ch], arr[ch, p]
+                    np.bitwise_or.at(mask, (par, code >> 5), np.left_shift(np.uint32(1), (code & 31).astype(np.uint32)))
+                    upar, at = np.unique(par, return_index=True)
+                    base[upar] = at
+            self._host.append((mask, base, ends))
+            self.n_nodes.append(cnt)
+            self.mask.append(torch.from_numpy(mask.view(np.int32)).to(device))
+            self.base.append(torch.from_numpy(base).to(device))
+            self.ends.append(torch.from_numpy(ends).to(device))
+            node, cnt, rows, firsts = nxt
+        self.n_nodes.append(cnt)
+
+
 class NCIModel:
     """`generate()` mirrors the reference call; weights use the reference's state_dict names
     (T5ForConditionalGeneration: shared, encoder.*, decoder.*, decode_embeddings, adaptor*, lm_head)."""
@@ -389,6 +466,7 @@ class NCIModel:
         self.prefix_table_queries = prefix_table_queries
         self._tables = None
         self._graphs = GraphCache()
+        self._len_pow = {}        # (max_length, length_penalty) -> f64 [max_length + 1] on the device (ops.VarBeamPool)
         c = self.cfg
         self.shared = _dev(weights, "shared.weight", self.dev)
         self.dec_emb = _dev(weights, "decode_embeddings.weight", self.dev)
@@ -482,6 +560,9 @@ class NCIModel:
         # decode_tree: None = the shared-sons tree of every script (TreeBuilder(share_sons=True): all K codes at every level),
         # or a PrefixTree = the reference's generic trie of the existing code paths (TreeBuilder(share_sons=False))
         tree = reference_kwargs.get("decode_tree")
+        if isinstance(tree, RaggedPrefixTree):
+            return self._generate_ragged(input_ids, attention_mask, R, length_penalty, max_length, graph, output_dec_hidden,
+                                         pad_encoder, tree)
         assert tree is None or (isinstance(tree, PrefixTree) and tree.M == c.M and tree.K == c.K), "decode_tree: a PrefixTree of this model's (M, K)"
         # K < R (SURVEY 8(a') note ii): the reference carries -1e9 placeholder beams until K**p real prefixes exist; they
         # never win against a real candidate, so the search keeps min(R, live * K) beams per level (golden G1 (3,8,10), (2,4,10))
@@ -499,6 +580,78 @@ class NCIModel:
             out = self._search(ids, mask, R, length_penalty, pack=not pad_encoder, tree=tree, keep_dec=output_dec_hidden)
         decoded, hyp, enc = out[:3]
         return decoded, hyp.reshape(-1).tolist(), enc, DecHidden(*out[3:]) if output_dec_hidden else None
+
+    def _generate_ragged(self, input_ids, attention_mask, R, length_penalty, max_length, graph, output_dec_hidden, pad_encoder,
+                         tree):
+        """generate() under a RaggedPrefixTree: (decoded i64 [B*R, max_length] -- eos after the last code where it fits,
+        then pad 0 --, scores list[float] descending per query, encoder states, None, lengths i32 [B*R] = tokens before
+        eos).  The search runs max_length - 1 steps whatever the data (`done` is data: one graph serves every batch).
+        Hypotheses with score -inf (fewer ids reachable than beams) carry placeholder tokens; the reference's are
+        unspecified there (ties among -inf candidates of torch.topk)."""
+        c = self.cfg
+        T = c.M + 2
+        if output_dec_hidden:
+            raise NotImplementedError("output_dec_hidden=True with a variable-depth decode tree is not built "
+                                      "(--query_encoder nci over --codebook 0)")
+        assert max_length in (None, T), "max_length must be the model's M + 2"
+        assert tree.K == c.K and tree.depth <= c.M + 1 and len(tree.mask) >= c.M + 1, \
+            "decode_tree: a RaggedPrefixTree of this model's K with levels=M + 1 and at most M + 1 codes per id"
+        assert 1 <= R <= 32 and c.K <= 256, "the variable-depth beam step takes R <= 32 beams and K <= 256 codes"
+        assert c.M + 1 <= 8, "variable-depth search: at most 8 decoder positions (the indexed K|V cache)"
+        ids = input_ids.to(self.dev, torch.int64).contiguous()
+        mask = attention_mask.to(self.dev, torch.int64).contiguous()
+        key = (T, float(length_penalty))
+        if key not in self._len_pow:
+            self._len_pow[key] = torch.tensor([float(l) ** float(length_penalty) for l in range(T + 1)],
+                                              dtype=torch.float64).to(self.dev)
+        len_pow = self._len_pow[key]
+        if graph and 0 < ids.shape[0] <= GRAPH_MAX_ROWS:
+            if self.prefix_table_bytes:
+                self.tables(R)
+            out = self._graphs.run(("generate_var", R, float(length_penalty), tree.serial) + tuple(ids.shape),
+                                   lambda i, m: self._search_var(i, m, R, len_pow, False, tree), ids, mask)
+        else:
+            out = self._search_var(ids, mask, R, len_pow, not pad_encoder, tree)
+        decoded, hyp, lengths, enc = out
+        return decoded, hyp.tolist(), enc, None, lengths
+
+    def _search_var(self, ids, mask, R, len_pow, pack, tree):
+        """The device part of the variable-depth search: all R beams from the first step (beams 1..R-1 seeded with -1e9,
+        generation_utils.py:745-750), M + 1 steps of mevi_beam_step_var_f32, then mevi_beam_finalize_var_f32."""
+        c = self.cfg
+        B, K, T = ids.shape[0], c.K, c.M + 2
+        enc = self.encoder.forward(self.shared, ids, mask, pack=None if pack else False)
+        xkv = self.decoder.cross_kv(enc, mask, pack=pack)
+        pool = ops.VarBeamPool(B, R, T, None, self.dev, len_pow=len_pow)
+        tokens = torch.zeros(B * R, dtype=torch.int64, device=self.dev)
+        scores = torch.zeros((B, R), dtype=torch.float32, device=self.dev)
+        scores[:, 1:] = -1e9
+        node = torch.zeros((B, R), dtype=torch.int32, device=self.dev)
+        prefix = torch.zeros((B, R, T), dtype=torch.int32, device=self.dev)
+        levels = self.tables(R).levels if self.prefix_table_bytes != 0 else 0
+        pidx = torch.zeros(B * R, dtype=torch.int64, device=self.dev)
+        dcache = self.decoder.new_cache(B * R)
+        anc = torch.zeros((B * R, 0), dtype=torch.int32, device=self.dev)
+        acache = self.adaptor.new_cache(B * R) if levels == 0 else None
+        base = torch.arange(B, device=self.dev)[:, None]
+        own = torch.arange(B * R, dtype=torch.int32, device=self.dev)[:, None]
+        for p in range(c.M + 1):
+            if p == levels and p > 0:
+                acache = self.tables().cache_rows(self.adaptor, pidx, p)
+            key_rows = torch.cat([anc, own], 1).contiguous()
+            logits = self._logits(tokens, p, dcache, acache, xkv, mask, R, pidx if p < levels else None, key_rows=key_rows)
+            scores, parent, code, node, prefix, anc = ops.beam_step_var(logits, scores, node, prefix, anc, K, p, tree.mask[p],
+                                                                        tree.base[p], tree.ends[p], pool)
+            if p == c.M:
+                break
+            rows = (base * R + parent.long()).reshape(-1)
+            if p >= levels:
+                acache = _reorder_cache(acache, rows, p + 1)
+            code = code.long().reshape(-1)
+            pidx = pidx[rows] * K + code
+            tokens = 2 + p * K + code
+        decoded, hyp, lengths = ops.beam_finalize_var(scores, prefix, pool)
+        return decoded, hyp, lengths, enc
 
     @torch.no_grad()
     def generate_all(self, input_ids, attention_mask, length_penalty=0.8, max_rows=1 << 16):

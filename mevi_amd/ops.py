@@ -882,3 +882,78 @@ def query_pool(mode, R, enc=None, mask=None, dec=None, emb_ids=None, emb_table=N
         hip.ptr(out), out.stride(0), hip.stream_ptr())
     hip.check(st, "mevi_query_pool_f32")
     return out
+
+
+class VarBeamPool:
+    """The hypothesis pools of a variable-depth search (BeamHypotheses of MEVI/transformers/generation_utils.py:1268-1315,
+    one of R slots per query) and the host-made table len ** length_penalty the kernels divide by (the reference divides
+    Python floats: f64, `int ** float`)."""
+
+    def __init__(self, nq, R, T, length_penalty, device, len_pow=None):
+        self.nq, self.R, self.T = nq, R, T
+        if len_pow is None:        # (a host -> device copy: pass `len_pow` when building the pool under graph capture)
+            len_pow = torch.tensor([float(l) ** float(length_penalty) for l in range(T + 1)], dtype=torch.float64).to(device)
+        assert len_pow.shape == (T + 1,) and len_pow.dtype == torch.float64
+        self.len_pow = len_pow
+        self.score = torch.zeros((nq, R), dtype=torch.float64, device=device)
+        self.seq = torch.zeros((nq, R), dtype=torch.int32, device=device)
+        self.len = torch.zeros((nq, R), dtype=torch.int32, device=device)
+        self.tok = torch.zeros((nq, R, T), dtype=torch.int32, device=device)
+        self.state = torch.zeros((nq, 4), dtype=torch.int32, device=device)      # entries, insertions, done, 0
+
+    def reset(self):
+        for t in (self.score, self.seq, self.len, self.tok, self.state):
+            t.zero_()
+
+
+@hip.on_device
+def beam_step_var(logits, beam_scores, node, prefix, anc, K, p, tree_mask, tree_base, tree_ends, pool):
+    """One step of the variable-depth beam search (mevi_beam_step_var_f32): logits f32 [nq*R, K+1], beam_scores f32 [nq, R],
+    node i32 [nq, R], prefix i32 [nq, R, T], anc i32 [nq*R, p] or None, the tree's level p (mask i32/u32 [n, ceil(K/32)], base
+    i32 [n], ends u8 [n]), pool a VarBeamPool (updated in place) -> (scores, parent, code, child node [nq, R], prefix
+    [nq, R, T], anc [nq*R, p+1] or None)."""
+    logits = _f32(logits).contiguous()
+    beam_scores = _f32(beam_scores).contiguous()
+    nq, R = beam_scores.shape
+    T = pool.T
+    assert (pool.nq, pool.R) == (nq, R) and logits.shape == (nq * R, K + 1)
+    assert node.shape == (nq, R) and node.dtype == torch.int32 and node.is_contiguous()
+    assert prefix.shape == (nq, R, T) and prefix.dtype == torch.int32 and prefix.is_contiguous()
+    n_nodes = tree_base.numel()
+    assert tree_mask.dtype == torch.int32 and tree_base.dtype == torch.int32 and tree_ends.dtype == torch.uint8
+    assert tree_mask.shape == (n_nodes, (K + 31) // 32) and tree_ends.shape == (n_nodes,)
+    assert tree_mask.is_contiguous() and tree_base.is_contiguous() and tree_ends.is_contiguous()
+    assert anc is None or (anc.shape == (nq * R, p) and anc.dtype == torch.int32 and anc.is_contiguous())
+    dev = logits.device
+    sc = torch.empty((nq, R), dtype=torch.float32, device=dev)
+    parent, code, child = (torch.empty((nq, R), dtype=torch.int32, device=dev) for _ in range(3))
+    out_prefix = torch.empty_like(prefix)
+    out_anc = None if anc is None else torch.empty((nq * R, p + 1), dtype=torch.int32, device=dev)
+    st = hip.lib().mevi_beam_step_var_f32(
+        hip.ptr(logits), hip.ptr(beam_scores), hip.ptr(node), hip.ptr(prefix), None if anc is None or p == 0 else hip.ptr(anc),
+        nq, R, K, p, T, hip.ptr(tree_mask) if n_nodes else None, hip.ptr(tree_base) if n_nodes else None,
+        hip.ptr(tree_ends) if n_nodes else None, n_nodes, hip.ptr(pool.len_pow), hip.ptr(pool.score), hip.ptr(pool.seq),
+        hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), hip.ptr(sc), hip.ptr(parent), hip.ptr(code), hip.ptr(child),
+        hip.ptr(out_prefix), None if out_anc is None else hip.ptr(out_anc), hip.stream_ptr())
+    hip.check(st, "mevi_beam_step_var_f32")
+    return sc, parent, code, child, out_prefix, out_anc
+
+
+@hip.on_device
+def beam_finalize_var(beam_scores, prefix, pool):
+    """The end of the variable-depth search (mevi_beam_finalize_var_f32): open beams of the queries that are not done join
+    their pools, every pool is written best first -> (decoded i64 [nq*R, T], scores f64 [nq*R], lengths i32 [nq*R])."""
+    beam_scores = _f32(beam_scores).contiguous()
+    nq, R = beam_scores.shape
+    T = pool.T
+    assert (pool.nq, pool.R) == (nq, R) and prefix.shape == (nq, R, T) and prefix.dtype == torch.int32 and prefix.is_contiguous()
+    dev = beam_scores.device
+    decoded = torch.empty((nq * R, T), dtype=torch.int64, device=dev)
+    scores = torch.empty(nq * R, dtype=torch.float64, device=dev)
+    lengths = torch.empty(nq * R, dtype=torch.int32, device=dev)
+    st = hip.lib().mevi_beam_finalize_var_f32(hip.ptr(beam_scores), hip.ptr(prefix), nq, R, T, hip.ptr(pool.len_pow),
+                                              hip.ptr(pool.score), hip.ptr(pool.seq), hip.ptr(pool.len), hip.ptr(pool.tok),
+                                              hip.ptr(pool.state), hip.ptr(decoded), hip.ptr(scores), hip.ptr(lengths),
+                                              hip.stream_ptr())
+    hip.check(st, "mevi_beam_finalize_var_f32")
+    return decoded, scores, lengths

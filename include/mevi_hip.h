@@ -516,7 +516,13 @@ int mevi_query_pool_f32(const float *enc, int64_t enc_ldb, int64_t enc_lds, cons
 /* Pieces of pq.beam_search (MEVI/pq.py:613-713; only reached with doc_multiclus > 1): the score row
  * -sum_k (x_k - c_k)^2 of every row against the K centroids of one level, and the residual hand-down
  * out[r] = x[src[r]] - centroids[code[r]].  The top-R step is mevi_beam_step_f32 with final_step = 2
- * (logits = the K score columns, candidate = beam_prob * softmax). */
+ * (logits = the K score columns, candidate = beam_prob * softmax).
+ *   Both: dim % 4 == 0; x and centroids (and gather_sub's out) 16-byte aligned, else MEVI_ERR_INVALID_ARG (rows are read
+ *   as float4); neg_dist itself needs only float alignment.  More rows than one launch covers (2^31 - 1 workgroups of
+ *   128 rows for neg_dist, of 4 rows for gather_sub): MEVI_ERR_UNSUPPORTED.  Every score is the sequential fmaf chain of
+ *   mevi_rq_encode_f32, bit for bit; gather_sub is one f32 subtraction per element.
+ *   Aliasing: src may repeat rows (beam fan-out).  out may be x itself only when src[r] == r for every r (the in-place
+ *   residual update of codebook training); any other overlap of out with x or centroids is undefined. */
 int mevi_rq_neg_dist_f32(const float *x, int64_t n, int64_t dim, const float *centroids, int64_t K,
                          float *neg_dist, void *stream);
 int mevi_gather_sub_f32(const float *x, const int64_t *src, const float *centroids, const int32_t *code,

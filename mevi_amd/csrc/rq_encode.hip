@@ -324,9 +324,11 @@ __global__ __launch_bounds__(256, 2) void rq_rows32_kernel(const float *__restri
 }
 
 // out[r] = X[src[r]] - C[code[r]]: the residual hand-down of pq.beam_search (pq.py:690-693). One wave per row.
-__global__ __launch_bounds__(256) void gather_sub_kernel(const float *__restrict__ X, const long long *__restrict__ src,
+// X and out carry no __restrict__: rq.train_rq_codebook updates its residual in place (out == X, src[r] == r) -- every
+// element is then read and written by the same lane, once.
+__global__ __launch_bounds__(256) void gather_sub_kernel(const float *X, const long long *__restrict__ src,
                                                         const float *__restrict__ C, const int *__restrict__ code,
-                                                        long long n, int dim, float *__restrict__ out) {
+                                                        long long n, int dim, float *out) {
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n) return;
   const int lane = threadIdx.x & 63;
@@ -402,7 +404,10 @@ extern "C" int mevi_rq_neg_dist_f32(const float *x, int64_t n, int64_t dim, cons
   MEVI_REQUIRE(n >= 0 && dim > 0 && K > 0 && dim % 4 == 0, MEVI_ERR_INVALID_ARG, "rq_neg_dist: bad shape");
   if (n == 0) return MEVI_OK;
   MEVI_REQUIRE(x && centroids && neg_dist, MEVI_ERR_INVALID_ARG, "rq_neg_dist: null pointer");
+  MEVI_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)centroids % 16) == 0, MEVI_ERR_INVALID_ARG,
+               "rq_neg_dist: x/centroids must be 16-byte aligned");
   const int64_t nblk = (n + RQ_ROWS - 1) / RQ_ROWS;
+  MEVI_REQUIRE(nblk <= 0x7fffffffLL, MEVI_ERR_UNSUPPORTED, "rq_neg_dist: too many rows");
   hipLaunchKernelGGL((rq_level_kernel<0, true>), dim3((unsigned)nblk), dim3(256), 0, stream, x, (long long)n, (int)dim,
                      centroids, 1, (int)K, (int *)nullptr, neg_dist);
   MEVI_HIP_CHECK(hipGetLastError());
@@ -414,7 +419,11 @@ extern "C" int mevi_gather_sub_f32(const float *x, const int64_t *src, const flo
   MEVI_REQUIRE(n >= 0 && dim > 0 && dim % 4 == 0, MEVI_ERR_INVALID_ARG, "gather_sub: bad shape");
   if (n == 0) return MEVI_OK;
   MEVI_REQUIRE(x && src && centroids && code && out, MEVI_ERR_INVALID_ARG, "gather_sub: null pointer");
-  hipLaunchKernelGGL(gather_sub_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), x,
+  MEVI_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)centroids % 16) == 0 && ((uintptr_t)out % 16) == 0, MEVI_ERR_INVALID_ARG,
+               "gather_sub: x/centroids/out must be 16-byte aligned");
+  const int64_t nblk = (n + 3) / 4;
+  MEVI_REQUIRE(nblk <= 0x7fffffffLL, MEVI_ERR_UNSUPPORTED, "gather_sub: too many rows");
+  hipLaunchKernelGGL(gather_sub_kernel, dim3((unsigned)nblk), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), x,
                      reinterpret_cast<const long long *>(src), centroids, code, (long long)n, (int)dim, out);
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;

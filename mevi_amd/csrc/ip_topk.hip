@@ -1864,6 +1864,26 @@ __global__ __launch_bounds__(256) void count_candidates_kernel(const unsigned in
 }
 
 // ---------------------------------------------------------------------------
+// Workspace layouts.  Every layout is a struct (members in memory order) with ONE function that fills it from a Carver and a
+// shape; its size is that same function run over a null base (carved_bytes), so byte count and pointers cannot drift apart.
+class Carver {
+  char *base_;
+  size_t used_ = 0;
+ public:
+  explicit Carver(void *base) : base_(static_cast<char *>(base)) {}  // null: count only
+  template <typename T> T *take(size_t count) {
+    T *p = base_ ? reinterpret_cast<T *>(base_ + used_) : nullptr;
+    used_ += align_up(count * sizeof(T), 256);
+    return p;
+  }
+  size_t used() const { return used_; }
+};
+template <typename F> static size_t carved_bytes(F &&carve) {
+  Carver count(nullptr);
+  carve(count);
+  return count.used();
+}
+
 struct SearchState {
   unsigned long long *buf;  // [nq, S]
   unsigned int *count;      // [nq]
@@ -1874,26 +1894,34 @@ struct SearchState {
                             //         zeroes set (L + 1) & 1 for the next
 };
 constexpr int TICKET_SLOTS = 2;
-
-static size_t state_bytes(int64_t nq, const TopkGeom &g) {
-  return align_up((size_t)nq * g.S * 8, 256) + 4 * align_up((size_t)nq * 4, 256) + align_up((size_t)TICKET_SLOTS * 8 * 4, 256);
+static SearchState carve_state(Carver &c, int64_t nq, const TopkGeom &g) {
+  return {c.take<unsigned long long>((size_t)nq * g.S), c.take<unsigned int>(nq), c.take<float>(nq), c.take<unsigned int>(nq),
+          c.take<float>(nq), c.take<unsigned int>(TICKET_SLOTS * 8)};
 }
 
-static SearchState carve_state(char *&p, int64_t nq, const TopkGeom &g) {
-  SearchState st;
-  st.buf = reinterpret_cast<unsigned long long *>(p);
-  p += align_up((size_t)nq * g.S * 8, 256);
-  st.count = reinterpret_cast<unsigned int *>(p);
-  p += align_up((size_t)nq * 4, 256);
-  st.tau = reinterpret_cast<float *>(p);
-  p += align_up((size_t)nq * 4, 256);
-  st.failed = reinterpret_cast<unsigned int *>(p);
-  p += align_up((size_t)nq * 4, 256);
-  st.tau_s = reinterpret_cast<float *>(p);
-  p += align_up((size_t)nq * 4, 256);
-  st.tickets = reinterpret_cast<unsigned int *>(p);
-  p += align_up((size_t)TICKET_SLOTS * 8 * 4, 256);
-  return st;
+// The exact search: main state, the guaranteed pass's state, its gathered queries and their row indices.
+struct ExactWs {
+  SearchState st, fb;
+  float *qsub; int *fidx;  // [nq, dim], [nq]
+  char *spare;             // 256 bytes the total has always carried; unused
+};
+static ExactWs carve_exact(Carver &c, int64_t nq, int64_t dim, const TopkGeom &g) {
+  return {carve_state(c, nq, g), carve_state(c, nq, g), c.take<float>((size_t)nq * dim), c.take<int>(nq), c.take<char>(256)};
+}
+
+// What the query split kernels write: the queries' image and four floats and a double per query.  The float arrays have
+// nq + 1 slots each: the one behind `norm` is err_bits, the other three are slack the totals have always carried.
+struct QuerySide {
+  float *image;
+  float *norm, *inv, *delta, *n16;  // ||q||, 1 / (S_q S_d), ||q - image / S_q|| (measured), ||image / S_q||
+  double *shift;                    // q.mu
+  unsigned int *err_bits;           // norm + nq: the largest observed error / proven bound of a prove step (float bits)
+};
+static QuerySide carve_query_side(Carver &c, int64_t nq, size_t image_bytes) {
+  QuerySide s = {reinterpret_cast<float *>(c.take<char>(image_bytes)), c.take<float>(nq + 1), c.take<float>(nq + 1),
+                 c.take<float>(nq + 1), c.take<float>(nq + 1), c.take<double>(nq), nullptr};
+  if (s.norm) s.err_bits = reinterpret_cast<unsigned int *>(s.norm + nq);
+  return s;
 }
 
 thread_local double g_growth = 0.0;
@@ -1926,25 +1954,31 @@ static void profile_collect() {
   g_events.clear();
 }
 
-// Walk docs [0, nd) in chunks; returns number of filter launches, <0 on error.
-static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, int dim,
-                        const TopkGeom &g, uint32_t id_base, const SearchState &st, bool guaranteed,
-                        hipStream_t stream, bool h1 = false, unsigned long long *cand = nullptr,
-                        const float *row_scale = nullptr /* non-null: Q, D = the 8-bit images (<= 32 queries), per-row scales */,
-                        const float *qub = nullptr /* ... and the queries' G_q */) {
-  const long long total = nq * (long long)g.k;
-  const long long init_n = total > nq ? total : nq;
-  const int n_tickets = TICKET_SLOTS * 8;
-  hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)(((init_n > n_tickets ? init_n : n_tickets) + 255) / 256)), dim3(256), 0, stream,
-                     st.buf, st.count, st.tau, st.failed, (long long)nq, g.S, g.k, st.tickets, n_tickets);
-  const size_t compact_lds = (size_t)g.S * 8 + 2048;  // keys + histogram
-  if (compact_lds > 65536) {  // dynamic LDS beyond 64 KiB must be opted into
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(compact_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)compact_lds) != hipSuccess) {
-      set_error("ip_topk: cannot raise dynamic LDS to %zu bytes", compact_lds);
-      return -1;
-    }
-  }
+// One walk of the corpus (run_pass).  The kind says what Q and D are: the f32 rows (the lists leave the pass ranked), centred
+// and scaled f16 images, or the 8-bit images (<= 32 queries; the caller checked the shape: i8_eligible); dim = their k extent.
+enum class PassKind { ExactF32, F16Image, I8Image };
+struct PassArgs {
+  PassKind kind;
+  const float *Q; int64_t nq;
+  const float *D; int64_t nd; int dim;
+  TopkGeom g; uint32_t id_base; SearchState st;
+  bool guaranteed;               // every chunk fits the candidate area: no query can overflow
+  unsigned long long *cand = nullptr;                 // the candidate counters of profiling level 2
+  const float *row_scale = nullptr, *qub = nullptr;   // I8Image only: per-row scales, the queries' G_q
+};
+
+// per (doc-tile pair, query tile) / persistent, one workgroup per CU / one per CU, each walking 256-row blocks of the chunk
+enum class FilterGrid { PerTile, PerCU, SmallStream };
+struct FilterChoice {
+  const void *fn;
+  size_t lds;    // dynamic LDS bytes
+  int qt, ni16;  // query-tile width; query blocks per wave of ip_filter_h16_kernel (0: another kernel, without its arguments)
+  FilterGrid grid;
+};
+
+// The filter kernel of a pass and how it is launched; false (error set) when the shape has none.
+static bool choose_filter(PassKind kind, int64_t nq, int dim, FilterChoice &f) {
+  const bool h1 = kind != PassKind::ExactF32;
   // Query-tile width: NI = 2 (128 query rows per workgroup).  NI = 4 (256 rows, 128
   // MFMAs per phase) was measured at the same MFMA-pipe utilisation (85.6 % vs 85.4 %)
   // and pads nq further, so only NI = 2 is instantiated.
@@ -1968,10 +2002,54 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
   }
   if (k16shape && dim / 32 < (ni16 == 2 ? 5 : ni16 == 4 ? 4 : 3)) {
     set_error("ip_topk: %d k units per tile are fewer than the filter ring's look-ahead", dim / 32);
-    return -1;
+    return false;
   }
-  const int qt = h1 ? (k16shape ? 32 * ni16 : H1_QT) : 64 * ni;
-  const int n_qtiles = (int)((nq + qt - 1) / qt);
+  f.qt = h1 ? (k16shape ? 32 * ni16 : H1_QT) : 64 * ni;
+  // stationary-query streaming kernel: few queries, and the query tile + rings + stash fit the 160 KiB of LDS
+  const bool small = kind == PassKind::I8Image ||
+                     (h1 && nq <= 32 && dim >= 160 && sm_lds_bytes(dim) + 8 * STASH_BYTES_PER_WAVE <= 160 * 1024 &&
+                      !getenv("MEVI_IP_TOPK_NO_SMALL"));
+  f.ni16 = k16shape && !small ? ni16 : 0;
+  const auto fn = [](auto *kernel) { return reinterpret_cast<const void *>(kernel); };
+  if (small) {
+    f.fn = kind == PassKind::I8Image ? fn(ip_filter_i8_small_kernel) : fn(ip_filter_h1_small_kernel);
+    f.lds = sm_lds_bytes(dim) + 8 * STASH_BYTES_PER_WAVE;
+    f.grid = FilterGrid::SmallStream;
+  } else if (h1) {  // MEVI_IP_FILTER_MFMA=32: the 32x32x16 form (A/B; same lists)
+    f.fn = !k16shape ? fn(ip_filter_h1_kernel)
+           : ni16 == 8 ? fn(ip_filter_h16_kernel<8>) : ni16 == 4 ? fn(ip_filter_h16_kernel<4>) : fn(ip_filter_h16_kernel<2>);
+    f.lds = h1_lds_bytes() + 8 * STASH_BYTES_PER_WAVE + 16 /* ip_filter_h16_kernel's ticket word */;
+    f.grid = FilterGrid::PerCU;
+  } else {
+    f.fn = (dim % BK) != 0 ? fn(ip_filter_kernel<2, true>) : fn(ip_filter_kernel<2, false>);
+    f.lds = pp_lds_bytes<2>();
+    f.grid = FilterGrid::PerTile;
+  }
+  return true;
+}
+
+// Walk docs [0, nd) in chunks; returns number of filter launches, <0 on error.
+static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
+  const int64_t nq = a.nq, nd = a.nd;
+  const TopkGeom &g = a.g;
+  const SearchState &st = a.st;
+  const bool guaranteed = a.guaranteed;
+  const long long total = nq * (long long)g.k;
+  const long long init_n = total > nq ? total : nq;
+  const int n_tickets = TICKET_SLOTS * 8;
+  hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)(((init_n > n_tickets ? init_n : n_tickets) + 255) / 256)), dim3(256), 0, stream,
+                     st.buf, st.count, st.tau, st.failed, (long long)nq, g.S, g.k, st.tickets, n_tickets);
+  const size_t compact_lds = (size_t)g.S * 8 + 2048;  // keys + histogram
+  if (compact_lds > 65536) {  // dynamic LDS beyond 64 KiB must be opted into
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(compact_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)compact_lds) != hipSuccess) {
+      set_error("ip_topk: cannot raise dynamic LDS to %zu bytes", compact_lds);
+      return -1;
+    }
+  }
+  FilterChoice f;
+  if (!choose_filter(a.kind, nq, a.dim, f)) return -1;
+  const int n_qtiles = (int)((nq + f.qt - 1) / f.qt);
   // expected survivors per chunk = k * growth = cap / growth_div (default 3: 3x head-room over the mean, tens of standard
   // deviations for exchangeable row order; a query that still overflows takes the guaranteed path)
   double growth_div = 3.0;
@@ -2001,29 +2079,9 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
     const int64_t v = atoll(e) / (2 * BM) * (2 * BM);
     if (v >= 2 * BM && v < cap_docs) cap_docs = v;
   }
-  size_t pp_lds = h1 ? h1_lds_bytes() + 8 * STASH_BYTES_PER_WAVE + 16 /* ip_filter_h16_kernel's ticket word */ : pp_lds_bytes<2>();
-  const bool ktail = (dim % BK) != 0;
-  const void *fn = nullptr;
-#define MEVI_PICK(NI_, T_) fn = reinterpret_cast<const void *>(ip_filter_kernel<NI_, T_>)
-  // stationary-query streaming kernel: few queries, and the query tile + rings + stash fit the 160 KiB of LDS
-  const bool small = row_scale != nullptr ||
-                     (h1 && nq <= 32 && dim >= 160 && sm_lds_bytes(dim) + 8 * STASH_BYTES_PER_WAVE <= 160 * 1024 &&
-                      !getenv("MEVI_IP_TOPK_NO_SMALL"));
-  if (row_scale) fn = reinterpret_cast<const void *>(ip_filter_i8_small_kernel);   // (the caller checked the shape: i8_eligible)
-  else if (small) fn = reinterpret_cast<const void *>(ip_filter_h1_small_kernel);
-  else if (h1) {  // Q, D = f16 images, dim = padded dim.  MEVI_IP_FILTER_MFMA=32: the 32x32x16 form (A/B; same lists)
-    fn = !k16shape ? reinterpret_cast<const void *>(ip_filter_h1_kernel)
-         : ni16 == 8 ? reinterpret_cast<const void *>(ip_filter_h16_kernel<8>)
-         : ni16 == 4 ? reinterpret_cast<const void *>(ip_filter_h16_kernel<4>)
-                     : reinterpret_cast<const void *>(ip_filter_h16_kernel<2>);
-  }
-  else if (ktail) MEVI_PICK(2, true);
-  else MEVI_PICK(2, false);
-#undef MEVI_PICK
-  if (small) pp_lds = sm_lds_bytes(dim) + 8 * STASH_BYTES_PER_WAVE;
   // opt in to > 64 KiB dynamic LDS (per device; cheap, so done on every call)
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp_lds) != hipSuccess) {
-    set_error("ip_topk: cannot raise dynamic LDS to %zu bytes", pp_lds);
+  if (hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds) != hipSuccess) {
+    set_error("ip_topk: cannot raise dynamic LDS to %zu bytes", f.lds);
     return -1;
   }
   int n_cu = 256;
@@ -2087,48 +2145,51 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
       return -1;
     }
     profile_mark(stream);
-{
+    {
       int nq_i = (int)nq, n_dp = (int)n_dtiles, n_qt = n_qtiles;
       long long d0 = (long long)seen, d1 = (long long)(seen + chunk);
       const float *tau_c = st.tau;
-      void *args[] = {(void *)&Q, &nq_i, (void *)&D, &d0, &d1, &dim, (void *)&tau_c, (void *)&st.buf,
-                      (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, &id_base, &n_qt, &n_dp};
+      // the thirteen arguments every filter kernel starts with, then its own
+      void *args[18] = {(void *)&a.Q, &nq_i, (void *)&a.D, &d0, &d1, (void *)&a.dim, (void *)&tau_c, (void *)&st.buf,
+                        (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, (void *)&a.id_base};
       unsigned grid = (unsigned)nwg;
-      if (h1) {  // persistent: one workgroup per CU (128 KiB of LDS each), a multiple of 8 so every XCD gets its share
-        const int64_t per_xcd = (nwg + 7) / 8 < n_cu / 8 ? (nwg + 7) / 8 : n_cu / 8;
-        grid = (unsigned)(8 * per_xcd);
-      }
-      // flush cadence of the 16x16 kernel's record stashes: with `seen` rows behind tau a chunk is expected to yield
-      // k * chunk / seen candidates per query (exchangeable row order; every row in the first chunk), i.e. r per 64 x 128
-      // wave tile; flush every T tiles with T r <= ~56 records (a stash holds 128)
       int flush_mask = H16_FLUSH_EVERY - 1;
-      {
+      // this launch's eight ticket counters (zero: init_state_kernel, or the launch before) and the next launch's, which it zeroes
+      unsigned int *tickets = st.tickets + 8 * (launches & 1), *tickets_next = st.tickets + 8 * ((launches + 1) & 1);
+      if (f.grid == FilterGrid::SmallStream) {
+        const int64_t nb = (chunk + 255) / 256;
+        grid = (unsigned)(nb < n_cu ? nb : n_cu);
+        args[13] = (void *)&a.row_scale;  // (ip_filter_h1_small_kernel stops at id_base)
+        args[14] = (void *)&a.qub;
+      } else {
+        if (f.grid == FilterGrid::PerCU) {  // 128 KiB of LDS each, a multiple of 8 so every XCD gets its share
+          const int64_t per_xcd = (nwg + 7) / 8 < n_cu / 8 ? (nwg + 7) / 8 : n_cu / 8;
+          grid = (unsigned)(8 * per_xcd);
+        }
+        args[13] = &n_qt;
+        args[14] = &n_dp;
+      }
+      if (f.ni16) {
+        // flush cadence of the 16x16 kernel's record stashes: with `seen` rows behind tau a chunk is expected to yield
+        // k * chunk / seen candidates per query (exchangeable row order; every row in the first chunk), i.e. r per 64 x 128
+        // wave tile; flush every T tiles with T r <= ~56 records (a stash holds 128)
         const double per_q = expect_per_q;
-        const double r = per_q / (double)chunk * 64.0 * 16.0 * (double)ni16;     // records per wave tile (64 rows x 16 NI queries)
+        const double r = per_q / (double)chunk * 64.0 * 16.0 * (double)f.ni16;     // records per wave tile (64 rows x 16 NI queries)
         int T = H16_FLUSH_EVERY;
         while (T > 1 && T * r > 56.0) T >>= 1;
         flush_mask = T - 1;
+        args[15] = &flush_mask;
+        args[16] = (void *)&tickets;
+        args[17] = (void *)&tickets_next;
       }
-      // this launch's eight ticket counters (zero: init_state_kernel, or the launch before) and the next launch's, which it zeroes
-      unsigned int *tickets = st.tickets + 8 * (launches & 1), *tickets_next = st.tickets + 8 * ((launches + 1) & 1);
-      void *args16[] = {(void *)&Q, &nq_i, (void *)&D, &d0, &d1, &dim, (void *)&tau_c, (void *)&st.buf,
-                        (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, &id_base, &n_qt, &n_dp, &flush_mask,
-                        (void *)&tickets, (void *)&tickets_next};
-      void *args_small[] = {(void *)&Q, &nq_i, (void *)&D, &d0, &d1, &dim, (void *)&tau_c, (void *)&st.buf,
-                            (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, &id_base, (void *)&row_scale, (void *)&qub};
-      if (small) {  // one workgroup per CU, each walking 256-row blocks of the chunk
-        const int64_t nb = (chunk + 255) / 256;
-        grid = (unsigned)(nb < n_cu ? nb : n_cu);
-      }
-      const bool k16 = k16shape && !small;
-      if (hipLaunchKernel(fn, dim3(grid), dim3(PP_THREADS), small ? args_small : (k16 ? args16 : args), pp_lds, stream) != hipSuccess) {
+      if (hipLaunchKernel(f.fn, dim3(grid), dim3(PP_THREADS), args, f.lds, stream) != hipSuccess) {
         set_error("ip_topk: filter kernel launch failed");
         return -1;
       }
     }
     profile_mark(stream);
-    if (cand)
-      hipLaunchKernelGGL(count_candidates_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, st.count, (int)nq, g.cap, cand);
+    if (a.cand)
+      hipLaunchKernelGGL(count_candidates_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, st.count, (int)nq, g.cap, a.cand);
     {
       const int nq_i = (int)nq;
       // one wave per query with the keys in registers first (MEVI_IP_TOPK_COMPACT=lds: the LDS kernel alone); what it leaves
@@ -2143,12 +2204,12 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
     if (sampled && seen + chunk >= nd)   // the sampled launch was the last: did k rows beat its threshold?
       hipLaunchKernelGGL(sample_check_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, st.tau, st.tau_s, st.failed, (int)nq);
     profile_mark(stream);
-    g_stats.filter_flops += 2.0 * (double)nq * (double)chunk * (double)dim;
+    g_stats.filter_flops += 2.0 * (double)nq * (double)chunk * (double)a.dim;
     if (g_profile) g_chunk_rows.push_back((long long)chunk);
     seen += chunk;
     ++launches;
   }
-  if (!h1)  // exact passes hand their lists out as ranked results (the f16 pass is re-scored and sorted later)
+  if (a.kind == PassKind::ExactF32)  // exact passes hand their lists out as ranked results (the f16 pass is re-scored and sorted later)
     hipLaunchKernelGGL(sort_lists_kernel, dim3((unsigned)nq), dim3(256), (size_t)next_pow2(g.k < 64 ? 64 : g.k) * 8, stream,
                        st.buf, g.S, g.k);
   if (hipGetLastError() != hipSuccess) {
@@ -2158,6 +2219,58 @@ static int64_t run_pass(const float *Q, int64_t nq, const float *D, int64_t nd, 
   return launches;
 }
 
+static void finalize(const unsigned long long *lists, int ld, int64_t k, int64_t nq, float *out_score, int64_t *out_id, hipStream_t stream) {
+  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((nq * (long long)k + 255) / 256)), dim3(256), 0, stream, lists, ld, (int)k,
+                     (long long)nq, out_score, reinterpret_cast<long long *>(out_id));
+}
+
+// Every search entry point starts its statistics (and the profiling events a failed call may have left) from nothing.
+static void begin_call() {
+  g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
+  for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
+  g_events.clear();
+}
+
+// Shape, pointer, alignment, id-range and workspace checks of a search, in the order and with the codes the entry points have
+// always had: a search that reads an index (`index_needed`) reports a misaligned workspace as MEVI_ERR_WORKSPACE, the exact
+// search as MEVI_ERR_INVALID_ARG, and only the latter bounds dim.  nq == 0 passes (the caller returns before it touches anything).
+static int check_search(const char *who, bool index_needed, const float *q, int64_t nq, const float *docs, const void *index,
+                        int64_t nd, int64_t dim, int64_t k, int64_t id_offset, const float *out_score, const int64_t *out_id,
+                        const void *workspace, size_t workspace_bytes, size_t need) {
+  MEVI_REQUIRE(nq >= 0 && nd >= 0 && dim > 0 && k > 0, MEVI_ERR_INVALID_ARG, "%s: bad shape nq=%lld nd=%lld dim=%lld k=%lld", who,
+               (long long)nq, (long long)nd, (long long)dim, (long long)k);
+  if (nq == 0) return MEVI_OK;
+  MEVI_REQUIRE(q && out_score && out_id && (index || !index_needed) && (docs || nd == 0), MEVI_ERR_INVALID_ARG, "%s: null pointer", who);
+  MEVI_REQUIRE(dim % 4 == 0 && k <= 4096, MEVI_ERR_UNSUPPORTED, "%s: dim %% 4 != 0 or k > 4096", who);
+  MEVI_REQUIRE((uintptr_t)q % 16 == 0 && (uintptr_t)docs % 16 == 0 && (uintptr_t)index % 256 == 0, MEVI_ERR_INVALID_ARG,
+               "%s: q/docs must be 16-byte, the index 256-byte aligned", who);
+  MEVI_REQUIRE(id_offset >= 0 && id_offset + nd < 0xFFFFFFFFLL && nq < (1LL << 31) && (index_needed || dim < (1LL << 24)),
+               MEVI_ERR_UNSUPPORTED, "%s: id_offset + nd, nq or dim out of range", who);
+  MEVI_REQUIRE(workspace && workspace_bytes >= need, MEVI_ERR_WORKSPACE, "%s: workspace %zu bytes < required %zu", who, workspace_bytes, need);
+  MEVI_REQUIRE((uintptr_t)workspace % 256 == 0, index_needed ? MEVI_ERR_WORKSPACE : MEVI_ERR_INVALID_ARG, "%s: misaligned workspace", who);
+  return MEVI_OK;
+}
+
+// The queries idx[] go through the guaranteed exact pass (no chunk larger than the candidate area) and their ranked lists to rows
+// idx[] of dst (row stride dst_ld).  restore_flops: the pass's work is not counted.  Synchronises (idx must outlive its copy).
+static int exact_repair(const float *q, const std::vector<int> &idx, const float *docs, int64_t nd, int dim, const TopkGeom &g,
+                        uint32_t id_base, const ExactWs &w, unsigned long long *dst, int dst_ld, bool restore_flops,
+                        hipStream_t stream) {
+  const int64_t nf = (int64_t)idx.size();
+  g_stats.n_failed_queries = nf;
+  MEVI_HIP_CHECK(hipMemcpyAsync(w.fidx, idx.data(), (size_t)nf * 4, hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)nf), dim3(256), 0, stream, q, w.fidx, (int)nf, dim, w.qsub);
+  const double keep_flops = g_stats.filter_flops;
+  const int64_t fl = run_pass({PassKind::ExactF32, w.qsub, nf, docs, nd, dim, g, id_base, w.fb, true}, stream);
+  if (restore_flops) g_stats.filter_flops = keep_flops;
+  if (fl < 0) return MEVI_ERR_HIP;
+  g_stats.n_fallback_chunks = fl;
+  hipLaunchKernelGGL(scatter_top_kernel, dim3((unsigned)nf), dim3(256), 0, stream, w.fb.buf, w.fidx, (int)nf, g.S, g.k, dst, dst_ld);
+  MEVI_HIP_CHECK(hipStreamSynchronize(stream));
+  profile_collect();
+  return MEVI_OK;
+}
+
 }  // namespace
 }  // namespace mevi
 
@@ -2165,9 +2278,7 @@ using namespace mevi;
 
 extern "C" size_t mevi_ip_topk_workspace_bytes(int64_t nq, int64_t dim, int64_t k) {
   if (nq <= 0 || k <= 0 || k > 4096 || dim <= 0) return 0;
-  const TopkGeom g = make_geom((int)k);
-  // main state + fallback state + gathered fallback queries + index list
-  return 2 * state_bytes(nq, g) + align_up((size_t)nq * dim * 4, 256) + align_up((size_t)nq * 4, 256) + 256;
+  return carved_bytes([&](Carver &c) { carve_exact(c, nq, dim, make_geom((int)k)); });
 }
 
 extern "C" int64_t mevi_ip_filter_tile_walk(int64_t n_dpairs, int64_t n_qtiles, int label, int32_t *dpair, int32_t *qtile) {
@@ -2194,35 +2305,18 @@ extern "C" int mevi_ip_topk_f32(const float *q, int64_t nq, const float *docs, i
                                 int64_t k, int64_t id_offset, float *out_score, int64_t *out_id,
                                 void *workspace, size_t workspace_bytes, void *stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
-  for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
-  g_events.clear();
-  MEVI_REQUIRE(nq >= 0 && nd >= 0 && dim > 0 && k > 0, MEVI_ERR_INVALID_ARG,
-               "ip_topk: bad shape nq=%lld nd=%lld dim=%lld k=%lld", (long long)nq, (long long)nd,
-               (long long)dim, (long long)k);
+  begin_call();
+  if (const int rc = check_search("ip_topk", false, q, nq, docs, nullptr, nd, dim, k, id_offset, out_score, out_id, workspace,
+                                  workspace_bytes, mevi_ip_topk_workspace_bytes(nq, dim, k)))
+    return rc;
   if (nq == 0) return MEVI_OK;
-  MEVI_REQUIRE(q && out_score && out_id && (docs || nd == 0), MEVI_ERR_INVALID_ARG, "ip_topk: null pointer");
-  MEVI_REQUIRE(dim % 4 == 0, MEVI_ERR_UNSUPPORTED, "ip_topk: dim=%lld must be a multiple of 4", (long long)dim);
-  MEVI_REQUIRE(k <= 4096, MEVI_ERR_UNSUPPORTED, "ip_topk: k=%lld > 4096 not supported", (long long)k);
-  MEVI_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)docs % 16) == 0, MEVI_ERR_INVALID_ARG,
-               "ip_topk: q/docs must be 16-byte aligned");
-  MEVI_REQUIRE(id_offset >= 0 && id_offset + nd < 0xFFFFFFFFLL, MEVI_ERR_UNSUPPORTED,
-               "ip_topk: id_offset + nd must be < 2^32-1");
-  MEVI_REQUIRE(nq < (1LL << 31) && dim < (1LL << 24), MEVI_ERR_UNSUPPORTED, "ip_topk: nq/dim too large");
-  const size_t need = mevi_ip_topk_workspace_bytes(nq, dim, k);
-  MEVI_REQUIRE(workspace && workspace_bytes >= need, MEVI_ERR_WORKSPACE,
-               "ip_topk: workspace %zu bytes < required %zu", workspace_bytes, need);
-  MEVI_REQUIRE(((uintptr_t)workspace % 256) == 0, MEVI_ERR_INVALID_ARG, "ip_topk: workspace must be 256-byte aligned");
 
   const TopkGeom g = make_geom((int)k);
-  char *p = reinterpret_cast<char *>(workspace);
-  SearchState st = carve_state(p, nq, g);
-  SearchState fb = carve_state(p, nq, g);
-  float *qsub = reinterpret_cast<float *>(p);
-  p += align_up((size_t)nq * dim * 4, 256);
-  int *fidx = reinterpret_cast<int *>(p);
+  Carver carver(workspace);
+  const ExactWs w = carve_exact(carver, nq, dim, g);
+  const SearchState &st = w.st;
 
-  int64_t launches = run_pass(q, nq, docs, nd, (int)dim, g, (uint32_t)id_offset, st, false, stream);
+  int64_t launches = run_pass({PassKind::ExactF32, q, nq, docs, nd, (int)dim, g, (uint32_t)id_offset, st, false}, stream);
   if (launches < 0) return MEVI_ERR_HIP;
   g_stats.n_chunks = launches;
 
@@ -2234,23 +2328,9 @@ extern "C" int mevi_ip_topk_f32(const float *q, int64_t nq, const float *docs, i
   std::vector<int> idx;
   for (int64_t i = 0; i < nq; ++i)
     if (failed[(size_t)i]) idx.push_back((int)i);
-  if (!idx.empty()) {
-    const int64_t nf = (int64_t)idx.size();
-    g_stats.n_failed_queries = nf;
-    MEVI_HIP_CHECK(hipMemcpyAsync(fidx, idx.data(), (size_t)nf * 4, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)nf), dim3(256), 0, stream, q, fidx, (int)nf, (int)dim, qsub);
-    int64_t fl = run_pass(qsub, nf, docs, nd, (int)dim, g, (uint32_t)id_offset, fb, true, stream);
-    if (fl < 0) return MEVI_ERR_HIP;
-    g_stats.n_fallback_chunks = fl;
-    hipLaunchKernelGGL(scatter_top_kernel, dim3((unsigned)nf), dim3(256), 0, stream, fb.buf, fidx, (int)nf, g.S, g.k, st.buf,
-                       g.S);
-    // idx (host) must outlive the async H2D copy
-    MEVI_HIP_CHECK(hipStreamSynchronize(stream));
-    profile_collect();
-  }
-  const long long total = nq * (long long)k;
-  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, st.buf, g.S,
-                     g.k, (long long)nq, out_score, reinterpret_cast<long long *>(out_id));
+  if (!idx.empty())  // (its work counts: this search's flops are those of both passes)
+    if (const int rc = exact_repair(q, idx, docs, nd, (int)dim, g, (uint32_t)id_offset, w, st.buf, g.S, false, stream)) return rc;
+  finalize(st.buf, g.S, k, nq, out_score, out_id, stream);
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;
 }
@@ -2272,22 +2352,17 @@ inline int64_t pad32(int64_t d) { return (d + 31) / 32 * 32; }
 // images are padded to whole PAIRS of 32-k units, at least four (the 16x16x32 tile stream alternates two fragment sets per unit
 // pair and keeps three units in flight)
 inline int64_t pad_k(int64_t d) { return (d + 63) / 64 * 64 < 128 ? 128 : (d + 63) / 64 * 64; }
-inline size_t index_image_bytes(int64_t nd, int64_t dim) { return align_up((size_t)image_rows(nd) * pad_k(dim) * 2, 256); }
-inline IndexView view_index(const void *index, int64_t nd, int64_t dim) {
-  const char *p = reinterpret_cast<const char *>(index);
+inline IndexView carve_index(Carver &c, int64_t nd, int64_t dim) {
   IndexView v;
-  v.image = reinterpret_cast<const float *>(p);
-  p += index_image_bytes(nd, dim);
-  v.norms_c = reinterpret_cast<const float *>(p);
-  p += align_up((size_t)nd * 4, 256);
-  v.mu = reinterpret_cast<const float *>(p);
-  p += align_up((size_t)pad_k(dim) * 4, 256);
-  v.bits = reinterpret_cast<const unsigned int *>(p);
-  v.scal = reinterpret_cast<const float *>(p + 16);
-  p += 256;
-  v.colsum = reinterpret_cast<double *>(const_cast<char *>(p));
+  v.image = reinterpret_cast<const float *>(c.take<char>((size_t)image_rows(nd) * pad_k(dim) * 2));
+  v.norms_c = c.take<float>((size_t)nd);
+  v.mu = c.take<float>((size_t)pad_k(dim));
+  v.bits = c.take<unsigned int>(64);  // one 256-byte slot: the maxima, then the scalars at byte 16
+  v.scal = v.bits ? reinterpret_cast<const float *>(v.bits + 4) : nullptr;
+  v.colsum = c.take<double>((size_t)pad_k(dim));
   return v;
 }
+inline IndexView view_index(const void *index, int64_t nd, int64_t dim) { Carver c(const_cast<void *>(index)); return carve_index(c, nd, dim); }
 // survivors kept per query: k plus a margin for the approximation error.  The margin has to cover the documents whose
 // approximate score lies within the error bound of the k-th one; their number grows with the density of scores at rank
 // k, i.e. with k -- a fixed floor of 128 made the re-scoring of a sharded search's short first-round lists (k/W + slack)
@@ -2304,8 +2379,7 @@ inline int h1_kprime(int k) {
 
 extern "C" size_t mevi_ip_index_bytes(int64_t nd, int64_t dim) {
   if (nd < 0 || dim <= 0) return 0;
-  return index_image_bytes(nd, dim) + align_up((size_t)nd * 4, 256) + align_up((size_t)pad_k(dim) * 4, 256) + 256 +
-         align_up((size_t)pad_k(dim) * 8, 256);
+  return carved_bytes([&](Carver &c) { carve_index(c, nd, dim); });
 }
 
 extern "C" int mevi_ip_index_build_f32(const float *docs, int64_t nd, int64_t dim, void *index, size_t index_bytes,
@@ -2319,8 +2393,7 @@ extern "C" int mevi_ip_index_build_f32(const float *docs, int64_t nd, int64_t di
   IndexView v = view_index(index, nd, dim);
   const int dimp = (int)pad_k(dim);
   // mean, maxima, scale and the scratch sums all start from zero (an empty shard keeps mu = 0, S_d = 1)
-  MEVI_HIP_CHECK(hipMemsetAsync(const_cast<float *>(v.mu), 0,
-                                align_up((size_t)dimp * 4, 256) + 256 + align_up((size_t)dimp * 8, 256), stream));
+  MEVI_HIP_CHECK(hipMemsetAsync(const_cast<float *>(v.mu), 0, (size_t)((const char *)(v.colsum + dimp) - (const char *)v.mu), stream));
   if (nd > 0) {
     MEVI_REQUIRE(docs, MEVI_ERR_INVALID_ARG, "ip_index_build: null docs");
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((nd + 511) / 512)), dim3(256), 0, stream, docs, (long long)nd,
@@ -2347,88 +2420,96 @@ inline int h1_kprime2(int k) {
   return kp2 <= 8192 ? kp2 : 0;
 }
 inline int64_t h1_second_pass_max(int64_t nq) { return (nq + 3) / 4; }
-inline size_t h1_second_pass_bytes(int64_t nq, int64_t dim, int64_t k) {
-  const int kp2 = h1_kprime2((int)k);
-  if (kp2 == 0) return 0;
-  const int64_t n2 = h1_second_pass_max(nq);
-  // state + exact lists + f32 and f16 query rows + norm / scale / shift + row indices
-  return state_bytes(n2, make_geom(kp2)) + align_up((size_t)n2 * k * 8, 256) + align_up((size_t)n2 * dim * 4, 256) +
-         align_up((size_t)image_rows(n2) * pad_k(dim) * 2, 256) + 4 * align_up((size_t)(n2 + 1) * 4, 256) +
-         align_up((size_t)n2 * 8, 256) + align_up((size_t)n2 * 4, 256);
+
+// One approximate pass and its proof: the state at the survivors' geometry, the exact lists, the query side.
+struct ApproxPass {
+  SearchState st;
+  unsigned long long *top;  // [nq, k] exact keys
+  QuerySide qs;
+};
+inline ApproxPass carve_approx(Carver &c, int64_t nq, int64_t k, const TopkGeom &gp, size_t image_bytes) {
+  return {carve_state(c, nq, gp), c.take<unsigned long long>((size_t)nq * k), carve_query_side(c, nq, image_bytes)};
+}
+inline ApproxPass carve_f16_pass(Carver &c, int64_t nq, int64_t dim, int64_t k, const TopkGeom &gp) {
+  return carve_approx(c, nq, k, gp, (size_t)image_rows(nq) * pad_k(dim) * 2);  // unit-major f16, whole 256-row blocks
+}
+// The whole indexed search.  The second pass is sized for the most queries it takes (absent when h1_kprime2(k) == 0); the
+// fallback uses the guaranteed pass's half of an exact search's workspace (exact.st stays unused: the total has always held it).
+struct IndexedWs {
+  ApproxPass first, second;
+  float *q2; int *idx2;          // the second pass's gathered queries [n2, dim] and their rows [n2]
+  ExactWs exact;
+  unsigned long long *counters;  // [3] candidate counters of the main pass (profiling level 2), one 256-byte slot
+};
+inline IndexedWs carve_indexed(Carver &c, int64_t nq, int64_t dim, int64_t k) {
+  IndexedWs w = {};
+  w.first = carve_f16_pass(c, nq, dim, k, make_geom(h1_kprime((int)k), nq));
+  if (const int kp2 = h1_kprime2((int)k)) {
+    const int64_t n2 = h1_second_pass_max(nq);
+    w.second = carve_f16_pass(c, n2, dim, k, make_geom(kp2));
+    w.q2 = c.take<float>((size_t)n2 * dim);
+    w.idx2 = c.take<int>(n2);
+  }
+  w.exact = carve_exact(c, nq, dim, make_geom((int)k));
+  w.counters = c.take<unsigned long long>(32);
+  return w;
+}
+
+// The prove step of an approximate pass: the exact f32 chains of its gp.k survivors per query (re-scored in place), the exact
+// top-k into `top`, and per query the proof that no row outside the survivors can belong to it (st.failed).  err_bits: null, or
+// where the largest observed error / proven bound goes; acc_k: null, or per query the approximate score below which a survivor
+// need not be re-scored; upper_keys = 1: the keys are upper bounds of the scores (the 8-bit image).
+void prove(const float *q, const float *docs, int64_t nq, int64_t dim, int64_t k, const TopkGeom &gp, uint32_t id_base,
+           const SearchState &st, const QuerySide &qs, unsigned long long *top, float c1, float c2, const unsigned int *bits,
+           const float *dnorms, unsigned int *err_bits, const float *acc_k, int upper_keys, hipStream_t stream) {
+  const int kp = gp.k, P = next_pow2(kp < 64 ? 64 : kp);
+  const long long waves = nq * (long long)((kp + 63) / 64);
+  hipLaunchKernelGGL(rescore_rows_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, q, docs, (int)dim, st.buf,
+                     gp.S, kp, (int)nq, (unsigned int)id_base, qs.norm, qs.inv, qs.shift, c1, c2, bits, dnorms, err_bits, qs.delta,
+                     qs.n16, acc_k, upper_keys);
+  hipLaunchKernelGGL(rescore_finish_kernel, dim3((unsigned)nq), dim3(256), (size_t)P * 8, stream, st.buf, gp.S, (int)k, kp,
+                     st.tau, qs.norm, qs.inv, qs.shift, c1, c2, bits, st.failed, top, (int)k, qs.delta, qs.n16);
 }
 }  // namespace
 
 extern "C" size_t mevi_ip_topk_indexed_workspace_bytes(int64_t nq, int64_t dim, int64_t k) {
   if (nq <= 0 || k <= 0 || k > 4096 || dim <= 0) return 0;
-  const TopkGeom gp = make_geom(h1_kprime((int)k), nq);
-  // approx state (K' geometry) + exact top lists + f16 queries + per-query norm / scale / shift, the second
-  // pass, then the exact-path workspace for the fallback
-  return state_bytes(nq, gp) + align_up((size_t)nq * k * 8, 256) + align_up((size_t)image_rows(nq) * pad_k(dim) * 2, 256) +
-         4 * align_up((size_t)(nq + 1) * 4, 256) + align_up((size_t)nq * 8, 256) + h1_second_pass_bytes(nq, dim, k) +
-         mevi_ip_topk_workspace_bytes(nq, dim, k) + 256;
+  return carved_bytes([&](Carver &c) { carve_indexed(c, nq, dim, k); });
 }
 
 extern "C" int mevi_ip_topk_indexed_f32(const float *q, int64_t nq, const float *docs, const void *index, int64_t nd,
                                         int64_t dim, int64_t k, int64_t id_offset, float *out_score,
                                         int64_t *out_id, void *workspace, size_t workspace_bytes, void *stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
-  for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
-  g_events.clear();
-  MEVI_REQUIRE(nq >= 0 && nd >= 0 && dim > 0 && k > 0, MEVI_ERR_INVALID_ARG, "ip_topk_indexed: bad shape");
+  begin_call();
+  if (const int rc = check_search("ip_topk_indexed", true, q, nq, docs, index, nd, dim, k, id_offset, out_score, out_id, workspace,
+                                  workspace_bytes, mevi_ip_topk_indexed_workspace_bytes(nq, dim, k)))
+    return rc;
   if (nq == 0) return MEVI_OK;
-  MEVI_REQUIRE(q && out_score && out_id && index && (docs || nd == 0), MEVI_ERR_INVALID_ARG, "ip_topk_indexed: null pointer");
-  MEVI_REQUIRE(dim % 4 == 0 && k <= 4096, MEVI_ERR_UNSUPPORTED, "ip_topk_indexed: dim %% 4 != 0 or k > 4096");
-  MEVI_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)docs % 16) == 0 && ((uintptr_t)index % 256) == 0,
-               MEVI_ERR_INVALID_ARG, "ip_topk_indexed: misaligned pointer");
-  MEVI_REQUIRE(id_offset >= 0 && id_offset + nd < 0xFFFFFFFFLL && nq < (1LL << 31), MEVI_ERR_UNSUPPORTED,
-               "ip_topk_indexed: ids / nq out of range");
-  const size_t need = mevi_ip_topk_indexed_workspace_bytes(nq, dim, k);
-  MEVI_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace % 256) == 0, MEVI_ERR_WORKSPACE,
-               "ip_topk_indexed: workspace %zu bytes < required %zu (or misaligned)", workspace_bytes, need);
 
   const int kp = h1_kprime((int)k);
   const TopkGeom gp = make_geom(kp, nq), g = make_geom((int)k);
   const int64_t dimp = pad_k(dim);
   IndexView iv = view_index(index, nd, dim);
-  char *p = reinterpret_cast<char *>(workspace);
-  SearchState st = carve_state(p, nq, gp);
-  unsigned long long *top = reinterpret_cast<unsigned long long *>(p);  // [nq, k] exact keys
-  p += align_up((size_t)nq * k * 8, 256);
-  float *qimage = reinterpret_cast<float *>(p);  // f16 image of the queries, unit-major, whole 256-row blocks
-  p += align_up((size_t)image_rows(nq) * dimp * 2, 256);
-  float *qnorm = reinterpret_cast<float *>(p);  // [nq] + 1 slot for the observed error ratio
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  float *qinv = reinterpret_cast<float *>(p);   // [nq] 1 / (S_q S_d)
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  float *qdelta = reinterpret_cast<float *>(p);  // [nq] ||q - f16 image / S_q||  (measured)
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  float *qn16 = reinterpret_cast<float *>(p);    // [nq] ||f16 image / S_q||
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  double *qshift = reinterpret_cast<double *>(p);  // [nq] q.mu
-  p += align_up((size_t)nq * 8, 256);
-  char *second_ws = p;
-  p += h1_second_pass_bytes(nq, dim, k);
-  void *exact_ws = p;
-  const size_t exact_ws_bytes = mevi_ip_topk_workspace_bytes(nq, dim, k);
+  Carver carver(workspace);
+  const IndexedWs w = carve_indexed(carver, nq, dim, k);
+  const SearchState &st = w.first.st;
+  const QuerySide &qs = w.first.qs;
+  unsigned long long *const top = w.first.top;
   const float c1 = h1_cacc(dimp), c2 = h1_c2(dim);   // c1: the accumulation constant of h1_err_bound (the roundings are measured)
-  // candidate counters of the main pass (profiling level 2): the spare 256 bytes behind the exact path's workspace
-  unsigned long long *cand = g_profile >= 2 ? reinterpret_cast<unsigned long long *>(p + exact_ws_bytes) : nullptr;
+  unsigned long long *cand = g_profile >= 2 ? w.counters : nullptr;
   if (cand) MEVI_HIP_CHECK(hipMemsetAsync(cand, 0, 32, stream));
 
   hipLaunchKernelGGL(split_queries_f16_kernel, dim3((unsigned)(image_rows(nq) / 4)), dim3(256), 0, stream, q, (long long)nq,
-                     (int)dim, (int)dimp, iv.mu, iv.scal, reinterpret_cast<_Float16 *>(qimage), qnorm, qinv, qshift, qdelta, qn16);
-  int64_t launches = run_pass(qimage, nq, iv.image, nd, (int)dimp, gp, (uint32_t)id_offset, st, false, stream, true, cand);
+                     (int)dim, (int)dimp, iv.mu, iv.scal, reinterpret_cast<_Float16 *>(qs.image), qs.norm, qs.inv, qs.shift, qs.delta,
+                     qs.n16);
+  int64_t launches = run_pass({PassKind::F16Image, qs.image, nq, iv.image, nd, (int)dimp, gp, (uint32_t)id_offset, st, false, cand}, stream);
   if (launches < 0) return MEVI_ERR_HIP;
   g_stats.n_chunks = launches;
   g_stats.filter_flops *= (double)dim / (double)dimp;  // algorithmic flops count dim, not the padding
   // exact re-scoring + verification
-  int P = 64;
-  while (P < kp) P <<= 1;
-  unsigned int *err_bits = reinterpret_cast<unsigned int *>(qnorm + nq);  // spare slot behind the norms (256-byte padded)
-  MEVI_HIP_CHECK(hipMemsetAsync(err_bits, 0, 4, stream));
+  MEVI_HIP_CHECK(hipMemsetAsync(qs.err_bits, 0, 4, stream));
   {
-    const long long waves = nq * (long long)((kp + 63) / 64);
     // the k-th best approximate score per query -> the exclusion threshold of the re-scoring (st.tau_s is free after the pass).
     // MEVI_IP_RESCORE_ALL=1: re-score every survivor (A/B; same lists)
     static const bool rescore_all = [] { const char *e = getenv("MEVI_IP_RESCORE_ALL"); return e && atoi(e) == 1; }();
@@ -2438,19 +2519,13 @@ extern "C" int mevi_ip_topk_indexed_f32(const float *q, int64_t nq, const float 
                          (float *)nullptr, st.tau_s);
       acc_k = st.tau_s;
     }
-    hipLaunchKernelGGL(rescore_rows_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, q, docs, (int)dim, st.buf,
-                       gp.S, kp, (int)nq, (unsigned int)id_offset, qnorm, qinv, qshift, c1, c2, iv.bits, iv.norms_c, err_bits, qdelta, qn16,
-                       acc_k);
-    hipLaunchKernelGGL(rescore_finish_kernel, dim3((unsigned)nq), dim3(256), (size_t)P * 8, stream, st.buf, gp.S, (int)k, kp,
-                       st.tau, qnorm, qinv, qshift, c1, c2, iv.bits, st.failed, top, (int)k, qdelta, qn16);
+    prove(q, docs, nq, dim, k, gp, (uint32_t)id_offset, st, qs, top, c1, c2, iv.bits, iv.norms_c, qs.err_bits, acc_k, 0, stream);
   }
   // the results are finalised BEFORE the host looks at the proof flags (the common case: every query proven); a repaired
   // list is finalised again below
-  const long long total = nq * (long long)k;
-  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, top, (int)k, (int)k,
-                     (long long)nq, out_score, reinterpret_cast<long long *>(out_id));
-  unsigned int err_host = 0;
-  MEVI_HIP_CHECK(hipMemcpyAsync(&err_host, err_bits, 4, hipMemcpyDeviceToHost, stream));
+  finalize(top, (int)k, k, nq, out_score, out_id, stream);
+  float err_ratio = 0.f;  // (max of float bits of non-negative ratios)
+  MEVI_HIP_CHECK(hipMemcpyAsync(&err_ratio, qs.err_bits, 4, hipMemcpyDeviceToHost, stream));
   unsigned long long cand_host[3] = {0ull, 0ull, 0ull};
   if (cand) MEVI_HIP_CHECK(hipMemcpyAsync(cand_host, cand, 24, hipMemcpyDeviceToHost, stream));
   MEVI_HIP_CHECK(hipGetLastError());
@@ -2458,15 +2533,11 @@ extern "C" int mevi_ip_topk_indexed_f32(const float *q, int64_t nq, const float 
   MEVI_HIP_CHECK(hipMemcpyAsync(failed.data(), st.failed, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
   MEVI_HIP_CHECK(hipStreamSynchronize(stream));
   profile_collect();
-  {
-    float r;
-    memcpy(&r, &err_host, 4);
-    g_stats.max_err_ratio = r;
-    g_stats.err_bound = 1.0;  // the ratio is observed error / proven bound
-    g_stats.n_filter_candidates = (int64_t)cand_host[0];
-    g_stats.max_launch_candidates = (int64_t)cand_host[1];
-    g_stats.n_list_overflows = (int64_t)cand_host[2];
-  }
+  g_stats.max_err_ratio = err_ratio;
+  g_stats.err_bound = 1.0;  // the ratio is observed error / proven bound
+  g_stats.n_filter_candidates = (int64_t)cand_host[0];
+  g_stats.max_launch_candidates = (int64_t)cand_host[1];
+  g_stats.n_list_overflows = (int64_t)cand_host[2];
   // approx-state overflow (adversarial order) is flagged by compact_kernel in the same array (bitwise or: both set 1)
   // Safety net for the proof itself: the bound must dominate every error actually observed on the re-scored
   // survivors (typically by 5-15x).  If an observation ever EXCEEDS it, the premise of the proofs is false and every query
@@ -2485,43 +2556,21 @@ extern "C" int mevi_ip_topk_indexed_f32(const float *q, int64_t nq, const float 
     const int64_t n2 = (int64_t)idx.size();
     g_stats.n_second_pass_queries = n2;
     const TopkGeom g2 = make_geom(kp2);
-    char *w = second_ws;
-    SearchState s2 = carve_state(w, h1_second_pass_max(nq), g2);
-    unsigned long long *top2 = reinterpret_cast<unsigned long long *>(w);
-    w += align_up((size_t)h1_second_pass_max(nq) * k * 8, 256);
-    float *q2 = reinterpret_cast<float *>(w);
-    w += align_up((size_t)h1_second_pass_max(nq) * dim * 4, 256);
-    float *qimage2 = reinterpret_cast<float *>(w);
-    w += align_up((size_t)image_rows(h1_second_pass_max(nq)) * dimp * 2, 256);
-    float *qnorm2 = reinterpret_cast<float *>(w);
-    w += align_up((size_t)(h1_second_pass_max(nq) + 1) * 4, 256);
-    float *qinv2 = reinterpret_cast<float *>(w);
-    w += align_up((size_t)(h1_second_pass_max(nq) + 1) * 4, 256);
-    float *qdelta2 = reinterpret_cast<float *>(w);
-    w += align_up((size_t)(h1_second_pass_max(nq) + 1) * 4, 256);
-    float *qn162 = reinterpret_cast<float *>(w);
-    w += align_up((size_t)(h1_second_pass_max(nq) + 1) * 4, 256);
-    double *qshift2 = reinterpret_cast<double *>(w);
-    w += align_up((size_t)h1_second_pass_max(nq) * 8, 256);
-    int *idx2 = reinterpret_cast<int *>(w);
-    MEVI_HIP_CHECK(hipMemcpyAsync(idx2, idx.data(), (size_t)n2 * 4, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)n2), dim3(256), 0, stream, q, idx2, (int)n2, (int)dim, q2);
-    hipLaunchKernelGGL(split_queries_f16_kernel, dim3((unsigned)(image_rows(n2) / 4)), dim3(256), 0, stream, q2, (long long)n2,
-                       (int)dim, (int)dimp, iv.mu, iv.scal, reinterpret_cast<_Float16 *>(qimage2), qnorm2, qinv2, qshift2, qdelta2, qn162);
+    const SearchState &s2 = w.second.st;
+    const QuerySide &qs2 = w.second.qs;
+    MEVI_HIP_CHECK(hipMemcpyAsync(w.idx2, idx.data(), (size_t)n2 * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)n2), dim3(256), 0, stream, q, w.idx2, (int)n2, (int)dim, w.q2);
+    hipLaunchKernelGGL(split_queries_f16_kernel, dim3((unsigned)(image_rows(n2) / 4)), dim3(256), 0, stream, w.q2, (long long)n2,
+                       (int)dim, (int)dimp, iv.mu, iv.scal, reinterpret_cast<_Float16 *>(qs2.image), qs2.norm, qs2.inv, qs2.shift,
+                       qs2.delta, qs2.n16);
     const double keep_flops = g_stats.filter_flops;
-    const int64_t l2 = run_pass(qimage2, n2, iv.image, nd, (int)dimp, g2, (uint32_t)id_offset, s2, false, stream, true);
+    const int64_t l2 = run_pass({PassKind::F16Image, qs2.image, n2, iv.image, nd, (int)dimp, g2, (uint32_t)id_offset, s2, false}, stream);
     g_stats.filter_flops = keep_flops;
     if (l2 < 0) return MEVI_ERR_HIP;
-    int P2 = 64;
-    while (P2 < kp2) P2 <<= 1;
-    const long long waves2 = n2 * (long long)((kp2 + 63) / 64);
-    hipLaunchKernelGGL(rescore_rows_kernel, dim3((unsigned)((waves2 + 3) / 4)), dim3(256), 0, stream, q2, docs, (int)dim, s2.buf,
-                       g2.S, kp2, (int)n2, (unsigned int)id_offset, qnorm2, qinv2, qshift2, c1, c2, iv.bits, iv.norms_c,
-                       (unsigned int *)nullptr, qdelta2, qn162, (const float *)nullptr);
-    hipLaunchKernelGGL(rescore_finish_kernel, dim3((unsigned)n2), dim3(256), (size_t)P2 * 8, stream, s2.buf, g2.S, (int)k, kp2,
-                       s2.tau, qnorm2, qinv2, qshift2, c1, c2, iv.bits, s2.failed, top2, (int)k, qdelta2, qn162);
+    prove(w.q2, docs, n2, dim, k, g2, (uint32_t)id_offset, s2, qs2, w.second.top, c1, c2, iv.bits, iv.norms_c, nullptr, nullptr, 0,
+          stream);
     // proven rows go to their place in `top` (unproven ones are overwritten by the exact path below)
-    hipLaunchKernelGGL(scatter_top_kernel, dim3((unsigned)n2), dim3(256), 0, stream, top2, idx2, (int)n2, (int)k, (int)k, top,
+    hipLaunchKernelGGL(scatter_top_kernel, dim3((unsigned)n2), dim3(256), 0, stream, w.second.top, w.idx2, (int)n2, (int)k, (int)k, top,
                        (int)k);
     std::vector<unsigned int> failed2((size_t)n2);
     MEVI_HIP_CHECK(hipMemcpyAsync(failed2.data(), s2.failed, (size_t)n2 * 4, hipMemcpyDeviceToHost, stream));
@@ -2532,31 +2581,9 @@ extern "C" int mevi_ip_topk_indexed_f32(const float *q, int64_t nq, const float 
       if (failed2[(size_t)i]) still.push_back(idx[(size_t)i]);
     idx.swap(still);
   }
-  if (!idx.empty()) {  // unproven or overflowed queries: exact f32 search of just those, scattered into `top`
-    const int64_t nf = (int64_t)idx.size();
-    g_stats.n_failed_queries = nf;
-    char *e = reinterpret_cast<char *>(exact_ws);
-    SearchState fb = carve_state(e, nq, g);
-    e += state_bytes(nq, g);  // skip the second state of the exact workspace layout
-    float *qsub = reinterpret_cast<float *>(e);
-    e += align_up((size_t)nq * dim * 4, 256);
-    int *fidx = reinterpret_cast<int *>(e);
-    (void)exact_ws_bytes;
-    MEVI_HIP_CHECK(hipMemcpyAsync(fidx, idx.data(), (size_t)nf * 4, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)nf), dim3(256), 0, stream, q, fidx, (int)nf, (int)dim, qsub);
-    const double keep_flops = g_stats.filter_flops;
-    int64_t fl = run_pass(qsub, nf, docs, nd, (int)dim, g, (uint32_t)id_offset, fb, true, stream);
-    g_stats.filter_flops = keep_flops;
-    if (fl < 0) return MEVI_ERR_HIP;
-    g_stats.n_fallback_chunks = fl;
-    hipLaunchKernelGGL(scatter_top_kernel, dim3((unsigned)nf), dim3(256), 0, stream, fb.buf, fidx, (int)nf, g.S, g.k, top,
-                       (int)k);
-    MEVI_HIP_CHECK(hipStreamSynchronize(stream));
-    profile_collect();
-  }
-  if (repaired)
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, top, (int)k, (int)k,
-                       (long long)nq, out_score, reinterpret_cast<long long *>(out_id));
+  if (!idx.empty())  // unproven or overflowed queries: exact f32 search of just those, scattered into `top`
+    if (const int rc = exact_repair(q, idx, docs, nd, (int)dim, g, (uint32_t)id_offset, w.exact, top, (int)k, true, stream)) return rc;
+  if (repaired) finalize(top, (int)k, k, nq, out_score, out_id, stream);
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;
 }
@@ -2572,23 +2599,17 @@ struct Index8View {
   const unsigned int *bits;  // [0] max ||y^||, [1] max ||d|| (from the f16 index), [2] rho, [3] 2^-20 rho max s_r, [4] max ||y - y^||, [5] max s_r, [6] eta = max ||I_r||  (float bits)
   double *colsq;             // [dimp] build scratch
 };
-inline size_t index8_image_bytes(int64_t nd, int64_t dim) { return align_up((size_t)image_rows(nd) * pad_k(dim), 256); }
-inline Index8View view_index8(const void *index8, int64_t nd, int64_t dim) {
-  const char *p = reinterpret_cast<const char *>(index8);
+inline Index8View carve_index8(Carver &c, int64_t nd, int64_t dim) {
   Index8View v;
-  v.image = reinterpret_cast<const float *>(p);
-  p += index8_image_bytes(nd, dim);
-  v.scale = reinterpret_cast<const float *>(p);
-  p += align_up((size_t)image_rows(nd) * 4, 256);
-  v.ynorm = reinterpret_cast<const float *>(p);
-  p += align_up((size_t)image_rows(nd) * 4, 256);
-  v.cscale = reinterpret_cast<const float *>(p);
-  p += align_up((size_t)pad_k(dim) * 4, 256);
-  v.bits = reinterpret_cast<const unsigned int *>(p);
-  p += 256;
-  v.colsq = reinterpret_cast<double *>(const_cast<char *>(p));
+  v.image = reinterpret_cast<const float *>(c.take<char>((size_t)image_rows(nd) * pad_k(dim)));
+  v.scale = c.take<float>((size_t)image_rows(nd));
+  v.ynorm = c.take<float>((size_t)image_rows(nd));
+  v.cscale = c.take<float>((size_t)pad_k(dim));
+  v.bits = c.take<unsigned int>(64);  // one 256-byte slot
+  v.colsq = c.take<double>((size_t)pad_k(dim));
   return v;
 }
+inline Index8View view_index8(const void *index8, int64_t nd, int64_t dim) { Carver c(const_cast<void *>(index8)); return carve_index8(c, nd, dim); }
 // survivors of the 8-bit pass.  A row's error term is ~0.2 of the score deviation (Gaussian rows): the K'-th key has to lie that
 // far below the k-th exact score -- 2.3 k rows at k = 1000 of 8.8 M i.i.d. rows: K' = 3 k + 64.  Measured at MS MARCO size
 // (profiles/r06_i8_small.txt): every list proven on the i.i.d., ANCE-scale and duplicates corpora; on the CLUSTERED corpus a
@@ -2611,17 +2632,23 @@ inline bool i8_eligible(int64_t nq, int64_t dim, int64_t k) {
   return nq >= 1 && nq <= 32 && k >= 1 && k <= 4096 && dim % 4 == 0 && dimp >= 256 && dimp <= 1024 &&
          sm_lds_bytes((int)dimp) + 8 * STASH_BYTES_PER_WAVE <= 160 * 1024 && h8_kprime((int)k) <= 4096;
 }
+// The 8-bit pass's own area, in front of the indexed search's workspace (eligible shapes only).
+struct I8Pass {
+  ApproxPass p;        // (the image: two int8 digit images of the 32-row query tile)
+  float *qub;          // [32] G_q
+  unsigned int *qbad;  // [32] queries the 8-bit pass must not answer
+};
+inline I8Pass carve_i8_pass(Carver &c, int64_t nq, int64_t dim, int64_t k) {
+  return {carve_approx(c, nq, k, make_geom(h8_kprime((int)k), nq), (size_t)pad_k(dim) * 64), c.take<float>(32), c.take<unsigned int>(32)};
+}
 inline size_t i8_own_workspace_bytes(int64_t nq, int64_t dim, int64_t k) {
-  const TopkGeom gp = make_geom(h8_kprime((int)k), nq);
-  return state_bytes(nq, gp) + align_up((size_t)nq * k * 8, 256) + align_up((size_t)pad_k(dim) * 64, 256) +
-         4 * align_up((size_t)(nq + 1) * 4, 256) + align_up((size_t)nq * 8, 256) + 512;
+  return i8_eligible(nq, dim, k) ? carved_bytes([&](Carver &c) { carve_i8_pass(c, nq, dim, k); }) : 0;
 }
 }  // namespace
 
 extern "C" size_t mevi_ip_index8_bytes(int64_t nd, int64_t dim) {
   if (nd < 0 || dim <= 0) return 0;
-  return index8_image_bytes(nd, dim) + 2 * align_up((size_t)image_rows(nd) * 4, 256) + align_up((size_t)pad_k(dim) * 4, 256) + 256 +
-         align_up((size_t)pad_k(dim) * 8, 256);
+  return carved_bytes([&](Carver &c) { carve_index8(c, nd, dim); });
 }
 
 extern "C" int mevi_ip_index8_build_f32(const float *docs, const void *index, int64_t nd, int64_t dim, void *index8,
@@ -2635,8 +2662,7 @@ extern "C" int mevi_ip_index8_build_f32(const float *docs, const void *index, in
   Index8View v = view_index8(index8, nd, dim);
   const int dimp = (int)pad_k(dim);
   // scales, maxima and the scratch sums start from zero
-  MEVI_HIP_CHECK(hipMemsetAsync(const_cast<float *>(v.cscale), 0,
-                                align_up((size_t)dimp * 4, 256) + 256 + align_up((size_t)dimp * 8, 256), stream));
+  MEVI_HIP_CHECK(hipMemsetAsync(const_cast<float *>(v.cscale), 0, (size_t)((const char *)(v.colsq + dimp) - (const char *)v.cscale), stream));
   if (nd > 0) {
     MEVI_REQUIRE(docs, MEVI_ERR_INVALID_ARG, "ip_index8_build: null docs");
     hipLaunchKernelGGL(colsq_kernel, dim3((unsigned)((nd + 511) / 512)), dim3(256), 0, stream, docs, (long long)nd, (int)dim, iv.mu, v.colsq);
@@ -2654,8 +2680,7 @@ extern "C" int mevi_ip_index8_build_f32(const float *docs, const void *index, in
 
 extern "C" size_t mevi_ip_topk_indexed8_workspace_bytes(int64_t nq, int64_t dim, int64_t k) {
   const size_t inner = mevi_ip_topk_indexed_workspace_bytes(nq, dim, k);
-  if (inner == 0) return 0;
-  return (i8_eligible(nq, dim, k) ? i8_own_workspace_bytes(nq, dim, k) : 0) + inner;
+  return inner ? i8_own_workspace_bytes(nq, dim, k) + inner : 0;
 }
 
 extern "C" int mevi_ip_topk_indexed8_f32(const float *q, int64_t nq, const float *docs, const void *index, const void *index8,
@@ -2670,75 +2695,44 @@ extern "C" int mevi_ip_topk_indexed8_f32(const float *q, int64_t nq, const float
                "ip_topk_indexed8: workspace %zu bytes < required %zu (or misaligned)", workspace_bytes, need);
   static const bool off = [] { const char *e = getenv("MEVI_IP_I8"); return e && atoi(e) == 0; }();
   const bool use8 = !off && index8 != nullptr && i8_eligible(nq, dim, k) && nd > 0;
-  const size_t own = i8_eligible(nq, dim, k) ? i8_own_workspace_bytes(nq, dim, k) : 0;
+  const size_t own = i8_own_workspace_bytes(nq, dim, k);
   char *inner_ws = reinterpret_cast<char *>(workspace) + own;
   const size_t inner_bytes = workspace_bytes - own;
   if (!use8)
     return mevi_ip_topk_indexed_f32(q, nq, docs, index, nd, dim, k, id_offset, out_score, out_id, inner_ws, inner_bytes, stream_);
 
-  MEVI_REQUIRE(q && out_score && out_id && index && docs, MEVI_ERR_INVALID_ARG, "ip_topk_indexed8: null pointer");
-  MEVI_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)docs % 16) == 0 && ((uintptr_t)index % 256) == 0 && ((uintptr_t)index8 % 256) == 0,
-               MEVI_ERR_INVALID_ARG, "ip_topk_indexed8: misaligned pointer");
-  MEVI_REQUIRE(id_offset >= 0 && id_offset + nd < 0xFFFFFFFFLL, MEVI_ERR_UNSUPPORTED, "ip_topk_indexed8: ids out of range");
-  g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
-  for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
-  g_events.clear();
-  const int kp = h8_kprime((int)k);
-  const TopkGeom gp = make_geom(kp, nq);
+  MEVI_REQUIRE(((uintptr_t)index8 % 256) == 0, MEVI_ERR_INVALID_ARG, "ip_topk_indexed8: the 8-bit index must be 256-byte aligned");
+  if (const int rc = check_search("ip_topk_indexed8", true, q, nq, docs, index, nd, dim, k, id_offset, out_score, out_id, workspace,
+                                  workspace_bytes, need))
+    return rc;
+  begin_call();
+  const TopkGeom gp = make_geom(h8_kprime((int)k), nq);
   const int64_t dimp = pad_k(dim);
   const IndexView iv = view_index(index, nd, dim);
   const Index8View v8 = view_index8(index8, nd, dim);
-  char *p = reinterpret_cast<char *>(workspace);
-  SearchState st = carve_state(p, nq, gp);
-  unsigned long long *top = reinterpret_cast<unsigned long long *>(p);
-  p += align_up((size_t)nq * k * 8, 256);
-  float *qimage = reinterpret_cast<float *>(p);  // two int8 digit images of the 32-row query tile
-  p += align_up((size_t)dimp * 64, 256);
-  float *qnorm = reinterpret_cast<float *>(p);
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  float *qinv = reinterpret_cast<float *>(p);
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  float *qdelta = reinterpret_cast<float *>(p);
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  float *qn16 = reinterpret_cast<float *>(p);
-  p += align_up((size_t)(nq + 1) * 4, 256);
-  double *qshift = reinterpret_cast<double *>(p);
-  p += align_up((size_t)nq * 8, 256);
-  float *qub = reinterpret_cast<float *>(p);       // [32] G_q
-  p += 256;
-  unsigned int *qbad = reinterpret_cast<unsigned int *>(p);   // [32] queries the 8-bit pass must not answer
+  Carver carver(workspace);
+  const I8Pass w = carve_i8_pass(carver, nq, dim, k);
+  const SearchState &st = w.p.st;
+  const QuerySide &qs = w.p.qs;
   const float c1 = (float)(1.001 / 4194304.0), c2 = h1_c2(dim);   // c1: three roundings of the key's float form (< 2^-22)
 
   hipLaunchKernelGGL(split_queries_i8_kernel, dim3(8), dim3(256), 0, stream, q, (int)nq, (int)dim, (int)dimp, iv.mu, v8.cscale,
-                     reinterpret_cast<signed char *>(qimage), qnorm, qinv, qshift, qdelta, qn16, v8.bits, qub, qbad);
-  const int64_t launches = run_pass(qimage, nq, v8.image, nd, (int)dimp, gp, (uint32_t)id_offset, st, false, stream, true, nullptr, v8.scale, qub);
+                     reinterpret_cast<signed char *>(qs.image), qs.norm, qs.inv, qs.shift, qs.delta, qs.n16, v8.bits, w.qub, w.qbad);
+  const int64_t launches = run_pass({PassKind::I8Image, qs.image, nq, v8.image, nd, (int)dimp, gp, (uint32_t)id_offset, st, false, nullptr,
+                                     v8.scale, w.qub}, stream);
   if (launches < 0) return MEVI_ERR_HIP;
-  int P = 64;
-  while (P < kp) P <<= 1;
-  unsigned int *err_bits = reinterpret_cast<unsigned int *>(qnorm + nq);
-  MEVI_HIP_CHECK(hipMemsetAsync(err_bits, 0, 4, stream));
-  {
-    const long long waves = nq * (long long)((kp + 63) / 64);
-    // every survivor is re-scored (the keys are upper bounds: no lower bound to exclude against)
-    hipLaunchKernelGGL(rescore_rows_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, q, docs, (int)dim, st.buf,
-                       gp.S, kp, (int)nq, (unsigned int)id_offset, qnorm, qinv, qshift, c1, c2, v8.bits, v8.ynorm, err_bits, qdelta, qn16,
-                       (const float *)nullptr, 1);
-    hipLaunchKernelGGL(rescore_finish_kernel, dim3((unsigned)nq), dim3(256), (size_t)P * 8, stream, st.buf, gp.S, (int)k, kp,
-                       st.tau, qnorm, qinv, qshift, c1, c2, v8.bits, st.failed, top, (int)k, qdelta, qn16);
-  }
-  const long long total = nq * (long long)k;
-  hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, top, (int)k, (int)k,
-                     (long long)nq, out_score, reinterpret_cast<long long *>(out_id));
-  unsigned int err_host = 0;
-  MEVI_HIP_CHECK(hipMemcpyAsync(&err_host, err_bits, 4, hipMemcpyDeviceToHost, stream));
+  MEVI_HIP_CHECK(hipMemsetAsync(qs.err_bits, 0, 4, stream));
+  // every survivor is re-scored (the keys are upper bounds: no lower bound to exclude against)
+  prove(q, docs, nq, dim, k, gp, (uint32_t)id_offset, st, qs, w.p.top, c1, c2, v8.bits, v8.ynorm, qs.err_bits, nullptr, 1, stream);
+  finalize(w.p.top, (int)k, k, nq, out_score, out_id, stream);
+  float ratio = 0.f;
+  MEVI_HIP_CHECK(hipMemcpyAsync(&ratio, qs.err_bits, 4, hipMemcpyDeviceToHost, stream));
   MEVI_HIP_CHECK(hipGetLastError());
   unsigned int failed[32], bad[32];
   MEVI_HIP_CHECK(hipMemcpyAsync(failed, st.failed, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
-  MEVI_HIP_CHECK(hipMemcpyAsync(bad, qbad, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+  MEVI_HIP_CHECK(hipMemcpyAsync(bad, w.qbad, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
   MEVI_HIP_CHECK(hipStreamSynchronize(stream));
   profile_collect();
-  float ratio;
-  memcpy(&ratio, &err_host, 4);
   int64_t open = 0;
   for (int64_t i = 0; i < nq; ++i) open += (failed[i] || bad[i]) ? 1 : 0;
   if (!(ratio <= 1.0f)) open = nq;   // an observation above the bound: its premise is false (as the f16 search's safety net)

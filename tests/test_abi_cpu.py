@@ -44,6 +44,36 @@ def test_workspace_queries_are_pure_host_arithmetic():
         assert ops.split_kp(k) == L.mevi_split_kp(k), k
 
 
+def test_workspace_and_index_sizes_are_those_of_the_recorded_commit():
+    """The five `*_bytes` entry points of the dense search over a grid of shapes (zeros for unsupported shapes included)
+    against tests/golden/ip_workspace_bytes.json, recorded by tools/capture_workspace_sizes.py from the commit before the
+    host code's layouts were rewritten: the footprint of a search and of an index is behaviour."""
+    import json
+
+    from mevi_amd import hip
+
+    with open(os.path.join(ROOT, "tests", "golden", "ip_workspace_bytes.json")) as f:
+        rec = json.load(f)
+    assert "parent commit" in rec["header"]
+    nq, dim, k, nd = rec["nq"], rec["dim"], rec["k"], rec["nd"]
+    assert nq == [0, 1, 31, 32, 33, 64, 65, 128, 129, 1024, 1025, 6980]
+    assert dim == [4, 36, 64, 100, 128, 160, 256, 768, 896, 960, 1024, 1028]
+    assert k == [1, 10, 32, 100, 1000, 1323, 1365, 4096, 4097]
+    assert nd == [0, 1, 255, 256, 257, 65536, 8841823]
+    L = hip.lib()
+    search = [(a, b, c) for a in nq for b in dim for c in k]
+    index = [(a, b) for a in nd for b in dim]
+    for name, shapes in (("mevi_ip_topk_workspace_bytes", search), ("mevi_ip_topk_indexed_workspace_bytes", search),
+                         ("mevi_ip_topk_indexed8_workspace_bytes", search), ("mevi_ip_index_bytes", index),
+                         ("mevi_ip_index8_bytes", index)):
+        want = rec[name]
+        assert len(want) == len(shapes), name
+        got = [getattr(L, name)(*s) for s in shapes]
+        wrong = [(s, g, w) for s, g, w in zip(shapes, got, want) if g != w]
+        assert not wrong, f"{name}: {len(wrong)} of {len(shapes)} differ, first {wrong[:3]} (shape, now, recorded)"
+        assert any(w > 0 for w in want), name
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
 

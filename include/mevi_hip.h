@@ -314,11 +314,14 @@ int mevi_attention_f32(const float *q, int64_t q_bs, int64_t q_ts, const float *
                        int64_t nb, int64_t tq, int64_t tk, int64_t heads, int64_t dh, int64_t kv_div,
                        const float *bias, int64_t bias_rows, int64_t bias_ld, int64_t q_pos0,
                        const int64_t *key_mask, int causal, float scale, const int64_t *kv_off, void *stream);
-/* One decode step of self-attention over beam-shared caches: row b attends to tk <= 8 cached positions, position j of
+/* One decode step of self-attention over beam-shared caches: row b attends to tk <= 16 cached positions, position j of
  * row b living in cache row key_rows[b * tk + j] (k / v[row, j, h*dh + d] via (k_bs, k_ts) / (v_bs, v_ts)).  The reference
  * re-orders every layer's K|V cache after each beam step (generation_utils.py:927-934 `_reorder_cache`: index_select of the
  * whole cache by the surviving beams' parents); here the caches stay where each step wrote them and the rows carry their
- * ancestors' indices -- same arithmetic as mevi_attention_f32 (tq = 1) on the re-ordered copy, bit for bit. */
+ * ancestors' indices -- same arithmetic as mevi_attention_f32 (tq = 1) on the re-ordered copy, bit for bit: tk <= 8 the
+ * eight-pairs-per-wave kernels, tk = 9 .. 16 the kernel mevi_attention_f32 itself takes at that shape with the rows fetched
+ * through key_rows (64-wide heads: the 16 x 16 matrix-core kernel; other widths: the fmaf chains, four (row, head) pairs
+ * per wave in 16-lane groups).  tk > 16 is refused. */
 int mevi_attention_cached_f32(const float *q, int64_t q_bs, const float *k, int64_t k_bs, int64_t k_ts, const float *v,
                               int64_t v_bs, int64_t v_ts, float *out, int64_t o_bs, int64_t nb, int64_t tk, int64_t heads,
                               int64_t dh, const int32_t *key_rows, const float *bias, int64_t bias_rows, int64_t bias_ld,
@@ -460,6 +463,22 @@ int mevi_beam_finalize_var_f32(const float *beam_scores, const int32_t *prefix, 
                                const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
                                int32_t *pool_tok, int32_t *pool_state, int64_t *decoded, double *scores, int32_t *lengths,
                                void *stream);
+
+/* The same step and finalize, same arguments and same contract word for word, for up to R <= 128 beams (pure-NCI eval: 100
+ * beams): one workgroup per query, the R*(K+1) candidates in dynamic LDS (129 KiB at R = 128, K = 256), 2R rounds of a
+ * workgroup-wide arg-max over the 64-bit (score | index) keys, the walk by a prefix count over the 2R ranks, the pool two
+ * slots per lane of one wavefront.  For R <= 32 every output and the pool are byte-identical to the narrow pair's.
+ * Refused before launch: R > 128, K > 256, T > 64, p + 1 >= T. */
+int mevi_beam_step_var_wide_f32(const float *logits, const float *beam_scores, const int32_t *node, const int32_t *prefix,
+                                const int32_t *anc, int64_t nq, int64_t R, int64_t K, int64_t p, int64_t T,
+                                const uint32_t *tree_mask, const int32_t *tree_base, const uint8_t *tree_ends, int64_t n_nodes,
+                                const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
+                                int32_t *pool_tok, int32_t *pool_state, float *out_scores, int32_t *out_parent,
+                                int32_t *out_code, int32_t *out_node, int32_t *out_prefix, int32_t *out_anc, void *stream);
+int mevi_beam_finalize_var_wide_f32(const float *beam_scores, const int32_t *prefix, int64_t nq, int64_t R, int64_t T,
+                                    const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
+                                    int32_t *pool_tok, int32_t *pool_state, int64_t *decoded, double *scores,
+                                    int32_t *lengths, void *stream);
 
 /* Row-wise (log-)softmax with the beam step's arithmetic (max, sum of expf(x - max), logf), for the branches that keep
  * EVERY candidate instead of a top-R: mode 0 = log_softmax of x f32 [rows, cols] (the all-paths walk `_generate_all`,

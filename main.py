@@ -4,7 +4,8 @@ path that marco_eval_nci_rq.sh drives (MEVI/main.py:356-794, 267-337).  Every fl
 accepted; the ones that configure training are parsed and ignored.  Only --mode eval with
 --codebook 1 --pq_type rq|pq --document_encoder ance|cocondenser|ar2 --query_encoder twin|nci --recall_level both|coarse|fine is built
 (+ the brute-force ablation --eval_all_documents 1 --recall_level fine --knn_topk_by_step 1, and --codebook 0 --label_length_cutoff L
---mapping_path ... --kary K: semantic ids of different lengths over the tower path)
+--mapping_path ... --kary K: semantic ids of different lengths over the tower path; and, without --document_encoder, the pure
+NCI baseline over those ids: the beams themselves are ranked, 100 of them by default)
 (the configuration of every shipped eval script); anything else raises.
 
 One process per GPU: `--n_gpu N` spawns N ranks itself like the reference (queries split by rank,
@@ -105,6 +106,14 @@ def parsers_parser(argv=None):
     args.mapping_path = given.get("--mapping_path")
     args.kary = int(given.get("--kary", 0))
     args.max_output_length = int(given.get("--max_output_length", 10))
+    # no --document_encoder: the NCI baseline -- semantic ids whatever --codebook says, ids cut to max_output_length - 2 codes
+    # unless --label_length_cutoff says otherwise, --query_encoder not read (MEVI/main.py:622-630, 776-787)
+    args.pure_nci = args.mode == "eval" and not args.document_encoder
+    if args.pure_nci:
+        args.codebook = 0
+        if args.label_length_cutoff <= 0:
+            args.label_length_cutoff = args.max_output_length - 2
+        args.max_output_length = min(args.max_output_length, args.label_length_cutoff + 2)
     if not args.codebook:
         ignored = [f for f in ignored if f[0] not in ("--label_length_cutoff", "--mapping_path", "--kary", "--max_output_length")]
     args.ignored_flags = ignored
@@ -187,6 +196,8 @@ def check_supported(a):
     if a.mode != "eval":
         raise SystemExit("mevi_amd builds the inference hot path only: use --mode eval, or --mode train --only_gen_rq 1 "
                          "for the offline index build (training is out of scope)")
+    if getattr(a, "pure_nci", False):
+        return check_pure_nci(a)
     if a.document_encoder not in ("ance", "cocondenser", "ar2"):
         raise SystemExit(f"main.py --mode eval: --document_encoder {a.document_encoder!r} is not built")
     if a.test_set != "dev":       # load_data_infer has no other branch (main_utils.py:238: the reference dies on df = None)
@@ -254,6 +265,46 @@ def check_semantic_ids(a):
     if a.num_return_sequences > 32 or a.kary > 256 or a.label_length_cutoff > 7:
         raise SystemExit(f"{what}: the variable-depth beam search takes --num_return_sequences <= 32, --kary <= 256 and "
                          "--label_length_cutoff <= 7")
+
+
+PURE_NCI_MAX_BEAMS, PURE_NCI_MAX_CUTOFF = 128, 15     # mevi_beam_step_var_wide_f32; 16 ancestor-indexed decoder positions
+
+
+def check_pure_nci(a):
+    """No --document_encoder: the NCI baseline (the reference's default; the row every table of the paper compares against).
+    The model generates --num_return_sequences ids under the tree of the --mapping_path ids cut to --label_length_cutoff
+    (default --max_output_length - 2) codes; recall / MRR are counted on the ids themselves (MEVI/main_models.py:3722-3780).
+    No tower, no corpus embeddings, no fine stage; --query_encoder is not read."""
+    what = "main.py --mode eval without --document_encoder"
+    if a.dataset != "marco":    # nq_dpr: answer-based hits need the documents of every generated id (main_models.py:3738-3757)
+        raise SystemExit(f"{what}: --dataset {a.dataset!r} is not built (only marco)")
+    if a.test_set != "dev":
+        raise SystemExit(f"{what}: --test_set {a.test_set!r} is not built (only 'dev')")
+    if a.recall_level != "coarse":     # the reference's own result handling only works with its default here
+        raise SystemExit(f"{what}: --recall_level {a.recall_level!r} is not built (only coarse: there is no fine stage)")
+    for k, v in (("use_topic_model", 0), ("eval_all_documents", 0), ("knn_topk_by_step", 0), ("doc_multiclus", 1)):
+        if getattr(a, k) != v:
+            raise SystemExit(f"{what}: --{k} {getattr(a, k)!r} is not built (only {v!r})")
+    if a.query_embedding_path:
+        raise SystemExit(f"{what}: --query_embedding_path is not built (no query embedding is read)")
+    if not a.mapping_path:
+        raise SystemExit(f"{what}: --mapping_path is required (pickle dict: document -> semantic id)")
+    if a.kary <= 0:
+        raise SystemExit(f"{what}: --kary > 0 is required (the codes of one level)")
+    if a.custom_save_path is None:
+        raise SystemExit(f"{what}: --custom_save_path is required")
+    if a.nci_ckpt is None and a.infer_ckpt is None:
+        raise SystemExit(f"{what}: --nci_ckpt or --infer_ckpt is required")
+    if a.label_length_cutoff < 1:
+        raise SystemExit(f"{what}: --max_output_length {a.max_output_length} leaves no code for the ids (needs >= 3)")
+    if a.num_return_sequences > PURE_NCI_MAX_BEAMS:
+        raise SystemExit(f"{what}: --num_return_sequences {a.num_return_sequences} is not built (the variable-depth beam "
+                         f"search takes <= {PURE_NCI_MAX_BEAMS} beams)")
+    if a.kary > 256:
+        raise SystemExit(f"{what}: --kary {a.kary} is not built (<= 256 codes per level)")
+    if a.label_length_cutoff > PURE_NCI_MAX_CUTOFF:
+        raise SystemExit(f"{what}: --label_length_cutoff {a.label_length_cutoff} (from --max_output_length) is not built "
+                         f"(<= {PURE_NCI_MAX_CUTOFF} codes)")
 
 
 QTOWER_PIECES = ("enc", "encmask", "dec", "emb")

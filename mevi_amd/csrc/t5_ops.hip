@@ -625,6 +625,67 @@ __global__ __launch_bounds__(256) void attention_few_keys_kernel(AttnArgs a) {
   }
 }
 
+// 9 .. 16 cached keys (variable-depth search over ids of up to 15 codes): the kernel above with 16-lane groups -- FOUR (row, head)
+// pairs per wave, lane 16 g + j scores key j of pair g, the group butterfly one step longer (xor 8, 4, 2, 1: the association
+// the 64-lane butterfly has on <= 16 non-zero lanes), then the 64 lanes are the output dims of one pair after the other.
+// Same chains, same bits as attention_kernel on the re-ordered copy.
+__global__ __launch_bounds__(256) void attention_keys16_kernel(AttnArgs a) {
+  const long long wid = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const long long npair = (long long)a.nb * a.H;
+  if (wid * 4 >= npair) return;
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, j = lane & 15;
+  const int dh = a.dh, tk = a.tk, qpos = a.q_pos0;
+  long long pair = wid * 4 + g;
+  if (pair >= npair) pair = npair - 1;
+  const int h = (int)(pair % a.H);
+  const int b = (int)(pair / a.H);
+  float s = -INFINITY;
+  if (j < tk) {
+    const long long bk = a.key_rows[(size_t)b * tk + j];
+    const float *q = a.q + (size_t)b * a.q_bs + (size_t)h * dh;
+    const float *kr = a.k + (size_t)bk * a.k_bs + (size_t)j * a.k_ts + (size_t)h * dh;
+    float acc = 0.f;
+    for (int d = 0; d < dh; d += 4) {
+      const float4 kv = *reinterpret_cast<const float4 *>(kr + d);
+      const float4 qv = *reinterpret_cast<const float4 *>(q + d);
+      acc = fmaf(qv.x * a.scale, kv.x, acc);
+      acc = fmaf(qv.y * a.scale, kv.y, acc);
+      acc = fmaf(qv.z * a.scale, kv.z, acc);
+      acc = fmaf(qv.w * a.scale, kv.w, acc);
+    }
+    float add = 0.f;
+    if (a.bias) add = a.bias[((size_t)h * a.bias_rows + qpos) * a.bias_ld + j];
+    if (a.causal && j > qpos) add += -1e9f;
+    s = acc + add;
+  }
+  float m = s;
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  const float e = j < tk ? expf(s - m) : 0.f;
+  float sum = e;
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+  const float p = e / sum;
+  for (int gg = 0; gg < 4; ++gg) {
+    const long long pr = wid * 4 + gg;
+    if (pr >= npair) break;  // wave-uniform
+    const int hh = (int)(pr % a.H);
+    const int bb = (int)(pr / a.H);
+    float acc0 = 0.f, acc1 = 0.f;
+    for (int jj = 0; jj < tk; ++jj) {
+      const long long vr = a.key_rows[(size_t)bb * tk + jj];
+      const float *vb = a.v + (size_t)vr * a.v_bs + (size_t)jj * a.v_ts + (size_t)hh * dh;
+      const float pj = __shfl(p, 16 * gg + jj);
+      if (lane < dh) acc0 = fmaf(pj, vb[lane], acc0);
+      if (lane + 64 < dh) acc1 = fmaf(pj, vb[lane + 64], acc1);
+    }
+    const size_t o_off = (size_t)bb * a.o_bs + (size_t)hh * dh;
+    if (lane < dh) put_ctx(a, o_off + lane, acc0);
+    if (lane + 64 < dh) put_ctx(a, o_off + lane + 64, acc1);
+  }
+}
+
 // The same kernel for 64- / 96-wide heads with the key rows and q TRANSPOSED THROUGH LDS.  Above, lane (g, j) walks its own
 // 256-byte key row with float4 loads: every load instruction of the wave touches 64 different cache lines (16 instructions
 // x 64 lines per wave; the context phase and q together ~200), so the per-key cost is the L1's line rate, not a bandwidth,
@@ -1469,11 +1530,13 @@ struct A16Work {
   const long long *mrow;
   float *sk, *sv, *smask;
   int nq, tk, qstep, h, KB, QB;
+  const int *krow;          // IDX only: key r lives in K|V batch row krow[r] (k_bs / v_bs apart), token r of that row
 };
 
 // KBM / QBM: key / query blocks of 16 the code is laid out for (1 or 2); a wave whose group needs one of each -- queries of up
 // to 16 tokens, ten beams -- runs the <1, 1> body: no block loops, no wave-uniform branches around them, half the registers
-template <int KBM, int QBM>
+// IDX: the keys are fetched through the ancestor table (attention_mfma16_indexed_kernel); everything after the loads is shared
+template <int KBM, int QBM, bool IDX = false>
 __device__ __forceinline__ void a16_body(const AttnArgs &a, const A16Work &wk) {
   const int lane = threadIdx.x & 63;
   const int n = lane & 15, kq = lane >> 4;
@@ -1520,8 +1583,14 @@ __device__ __forceinline__ void a16_body(const AttnArgs &a, const A16Work &wk) {
     const int r = 4 * it + kq;
     if (tk > 0) {
       const int rk = min(r, tk - 1);
-      k4[it] = *reinterpret_cast<const float4 *>(kg + (unsigned)(rk * k_rs32 + 4 * n));
-      v4[it] = *reinterpret_cast<const float4 *>(vg + (unsigned)(rk * v_rs32 + 4 * n));
+      if constexpr (IDX) {
+        const size_t row = (size_t)wk.krow[rk];
+        k4[it] = *reinterpret_cast<const float4 *>(kg + row * (size_t)a.k_bs + (size_t)rk * k_rs + 4 * n);
+        v4[it] = *reinterpret_cast<const float4 *>(vg + row * (size_t)a.v_bs + (size_t)rk * v_rs + 4 * n);
+      } else {
+        k4[it] = *reinterpret_cast<const float4 *>(kg + (unsigned)(rk * k_rs32 + 4 * n));
+        v4[it] = *reinterpret_cast<const float4 *>(vg + (unsigned)(rk * v_rs32 + 4 * n));
+      }
     } else {
       k4[it] = v4[it] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -1724,8 +1793,32 @@ __global__ __launch_bounds__(256, 2) void attention_mfma16_kernel(AttnArgs a, in
   wk.qg = qg, wk.kg = kg, wk.vg = vg, wk.ooff = ooff, wk.q_rs = q_rs, wk.o_rs = o_rs, wk.k_rs = k_rs, wk.v_rs = v_rs;
   wk.mrow = mrow, wk.sk = sk, wk.sv = sv, wk.smask = smask, wk.nq = nq, wk.tk = tk, wk.qstep = qstep, wk.h = h;
   wk.KB = (tk + 15) >> 4, wk.QB = (nq + 15) >> 4;      // <= 2 each (wave-uniform)
+  wk.krow = nullptr;
   if (wk.KB == 1 && wk.QB == 1) a16_body<1, 1>(a, wk);
   else if (wk.KB + wk.QB > 0) a16_body<2, 2>(a, wk);
+}
+
+// One decode-step row against 9 .. 16 cached keys of 64-wide heads, the keys named by the ancestor table: what mode 1 of the
+// kernel above computes for kv_div = 1 (one wave per (row, head), one key block, one query column) on the re-ordered copy of
+// the caches, without the copy -- same instructions after the loads, same bits.
+__global__ __launch_bounds__(256, 2) void attention_mfma16_indexed_kernel(AttnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int D = 64;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  float *sk = sm + (size_t)w * A16_WAVE_FLOATS, *sv = sk + 32 * A16_LD, *smask = sv + 32 * A16_LD;
+  const long long pair = (long long)blockIdx.x * 4 + w;
+  if (pair >= (long long)a.nb * a.H) return;            // wave-uniform; no workgroup barrier below
+  const long long gi = pair / a.H;
+  const int h = (int)(pair - gi * a.H);
+  A16Work wk;
+  wk.qg = a.q + (size_t)gi * a.q_bs + (size_t)h * D;
+  wk.kg = a.k + (size_t)h * D, wk.vg = a.v + (size_t)h * D;
+  wk.krow = a.key_rows + (size_t)gi * a.tk;
+  wk.ooff = (size_t)gi * a.o_bs + (size_t)h * D;
+  wk.q_rs = a.q_bs, wk.o_rs = a.o_bs, wk.k_rs = a.k_ts, wk.v_rs = a.v_ts;
+  wk.mrow = nullptr, wk.sk = sk, wk.sv = sv, wk.smask = smask, wk.nq = 1, wk.tk = a.tk, wk.qstep = 0, wk.h = h;
+  wk.KB = 1, wk.QB = 1;                                 // 9 <= tk <= 16 (the launcher)
+  a16_body<1, 1, true>(a, wk);
 }
 
 // logits[row, c] = sum_d s[row, d] * (T[trow, c*dim + d] + E[c, d]); one wave per (row, c); trow = row, or
@@ -2141,8 +2234,8 @@ static int attention_cached_launch(const float *q, int64_t q_bs, const float *k,
                                          int64_t heads, int64_t dh, const int32_t *key_rows, const float *bias,
                                          int64_t bias_rows, int64_t bias_ld, int64_t q_pos0, int causal, float scale,
                                          CtxImage ci, void *stream) {
-  MEVI_REQUIRE(nb >= 0 && tk > 0 && tk <= 8 && heads > 0 && dh > 0 && dh <= 128 && dh % 4 == 0, MEVI_ERR_UNSUPPORTED,
-               "attention_cached: 1..8 cached positions, head width a multiple of 4 up to 128 (got tk %lld, dh %lld)",
+  MEVI_REQUIRE(nb >= 0 && tk > 0 && tk <= 16 && heads > 0 && dh > 0 && dh <= 128 && dh % 4 == 0, MEVI_ERR_UNSUPPORTED,
+               "attention_cached: 1..16 cached positions, head width a multiple of 4 up to 128 (got tk %lld, dh %lld)",
                (long long)tk, (long long)dh);
   MEVI_REQUIRE(q_bs % 4 == 0 && k_bs % 4 == 0 && k_ts % 4 == 0 && v_bs % 4 == 0 && v_ts % 4 == 0, MEVI_ERR_INVALID_ARG,
                "attention_cached: strides must be multiples of 4");
@@ -2160,6 +2253,20 @@ static int attention_cached_launch(const float *q, int64_t q_bs, const float *k,
   a.seq_off = nullptr; a.kv_off = nullptr;
   a.key_rows = key_rows;
   MEVI_REQUIRE(nb * heads < (1LL << 31) - 8, MEVI_ERR_UNSUPPORTED, "attention_cached: too many (row, head) pairs");
+  if (tk > 8) {
+    // 9 .. 16 keys: the kernel attention_launch picks for (tq 1, this tk, kv_div 1) on a re-ordered copy, fed through key_rows
+    const bool mfma16_aligned = o_bs % 4 == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0;
+    if (dh == AM_D && short_mfma() && mfma16_aligned) {
+      MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_mfma16_indexed_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)A16_LDS));
+      hipLaunchKernelGGL(attention_mfma16_indexed_kernel, dim3((unsigned)((nb * heads + 3) / 4)), dim3(256), A16_LDS,
+                         (hipStream_t)stream, a);
+    } else {
+      hipLaunchKernelGGL(attention_keys16_kernel, dim3(blocks4((nb * heads + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    }
+    MEVI_HIP_CHECK(hipGetLastError());
+    return MEVI_OK;
+  }
   hipLaunchKernelGGL(few_keys_kernel(dh, tk), dim3(blocks4((nb * heads + 7) / 8)), dim3(256), 0, (hipStream_t)stream, a);
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;

@@ -296,17 +296,21 @@ class EvalRun:
         self.semantic = not getattr(a, "codebook", 1)
         if self.semantic:
             self.M, self.K = a.label_length_cutoff, a.kary
+        # no --document_encoder (main.check_pure_nci): the NCI baseline -- the generated ids themselves are ranked; no tower,
+        # no corpus embeddings, no fine stage (MEVI/main_models.py:3722-3780 with document_encoder None)
+        self.pure = bool(getattr(a, "pure_nci", False))
+        assert not self.pure or self.semantic
         tower_override, ckpt_codebook = {}, None
         # --query_encoder nci: the fine stage pools the NCI model's own states per (query, beam) (T5FineTuner.clus_repr);
         # the query tower is neither loaded nor run
-        self.nci_query = getattr(a, "query_encoder", "twin") == "nci"
+        self.nci_query = getattr(a, "query_encoder", "twin") == "nci" and not self.pure
         if self.nci_query:
             self.qpool_mode = ops.qpool_mode(a.qtower, a.query_embed_accum)
             self.atten = None
         # The 27 GB corpus upload (file reads + PCIe: ~0.8 s, 8 reader threads) and the checkpoint loads / model build below
         # (one Python thread: ~0.8 s) need different resources: the upload starts NOW on a background thread and is joined
         # where `self.emb` is first needed.  Only when the row width is known without loading the tower (T5-ANCE: config.json).
-        emb_job = self._start_corpus_upload(a)
+        emb_job = None if self.pure else self._start_corpus_upload(a)
         if getattr(a, "infer_ckpt", None):        # whole-model checkpoint (MEVI/main.py:203-230) takes precedence
             sd = _state_dict(a.infer_ckpt)
             nci_w, tower_override, ckpt_codebook = split_whole_checkpoint(sd, bool(getattr(a, "not_load_document_encoder", 0)))
@@ -337,7 +341,7 @@ class EvalRun:
         # the tower and its tokenizer (init_document_encoder, MEVI/main_models.py:1643-1681)
         enc = getattr(a, "document_encoder", None) or "ance"
         tower_dir = os.path.join(a.ckpt_dir, "t5-ance")       # NCI shares the T5-ANCE vocabulary in every configuration
-        if self.nci_query:
+        if self.nci_query or self.pure:
             self.tower = None
         elif enc == "ance":
             tw, tdims = load_tower_weights(tower_dir)
@@ -360,7 +364,7 @@ class EvalRun:
         # bert-base-uncased, special tokens only for 'ar2' (main_models.py:359-360)
         self.tower_tokenizer = tower_tokenizer
         self.tower_special_tokens = enc in ("ance", "ar2")
-        if enc != "ance" and tower_tokenizer is None and not self.nci_query:
+        if enc != "ance" and tower_tokenizer is None and not self.nci_query and not self.pure:
             from transformers import AutoTokenizer
 
             local = os.path.join(a.ckpt_dir, "bert-base-uncased")
@@ -368,6 +372,11 @@ class EvalRun:
                                                                  do_lower_case=True)
         # corpus embeddings resident in HBM (the reference keeps a CPU memmap and copies per cluster)
         # the corpus embeddings and the RQ codebook live in the query embedding's space: the tower's, or the NCI model's
+        if self.pure:
+            self.emb = self.fine = None
+            self._init_semantic_ids(a, None)
+            self._init_logs(a, rank, nrank, self.cfg.d_model)
+            return
         d_model = self.cfg.d_model if self.nci_query else self.tower.dim
         n_docs = os.path.getsize(a.embedding_path) // (4 * d_model)
         if emb_job is not None and emb_job[1] == d_model:
@@ -399,8 +408,11 @@ class EvalRun:
         t0 = time.perf_counter()
         with open(a.mapping_path, "rb") as f:
             mapping = pickle.load(f)
+        if n_docs is None:                  # the NCI baseline reads no corpus file: the mapping names the documents
+            n_docs = len(mapping)
         if sorted(mapping) != list(range(len(mapping))) or len(mapping) != n_docs:
-            raise SystemExit(f"--mapping_path: needs one id per document 0 .. {n_docs - 1} of --embedding_path "
+            raise SystemExit(f"--mapping_path: needs one id per document 0 .. {n_docs - 1}"
+                             f"{'' if self.pure else ' of --embedding_path'} "
                              f"({len(mapping)} entries found)")
         L = self.M
         codes = np.zeros((n_docs, L), np.int64)                 # code + 1, 0 = beyond the id's end
@@ -514,9 +526,12 @@ class EvalRun:
         # --recall_level: 'both' (the eval scripts), 'coarse' (beam clusters only: no tower pass, no fine stage) or 'fine'
         # (fine list only; main_models.py:3736,3781,4103-4110)
         self.level = "fine" if self.eval_all else getattr(a, "recall_level", "both")
+        if self.pure:                           # the ids are the result: one coarse log, no _fine / _hn files
+            self.level = "coarse"
         self.coarse_log = RankLog(f"{prefix}_coarse.tsv", rank, nrank, self.barrier) if self.level in ("coarse", "both") else None
         self.fine_log = RankLog(f"{prefix}_fine.tsv", rank, nrank, self.barrier) if self.level in ("fine", "both") else None
-        self.hn_log = RankLog(f"{prefix}_hn{a.save_hard_neg}.tsv", rank, nrank, self.barrier) if a.save_hard_neg else None
+        self.hn_log = RankLog(f"{prefix}_hn{a.save_hard_neg}.tsv", rank, nrank, self.barrier) \
+            if a.save_hard_neg and not self.pure else None      # (MEVI/main.py:630: no --document_encoder, no hard negatives)
 
     def tokenize(self, queries):
         out = encode_batch(self.tokenizer, queries, 32)
@@ -696,13 +711,13 @@ class EvalRun:
             t1 = time.time()
             self.timer["nci"].append(t1 - t0)
         if not want_f:      # recall_level 'coarse': cluster ranks and the candidate count only (main_models.py:3736-3780)
-            ndoc = self.fine.candidates_device(codes)[3]
+            ndoc = self.fine.candidates_device(codes)[3] if self.fine is not None else None    # NCI baseline: `length = None`
             results = []
             for i, text in enumerate(texts):
                 d = beam_lists[i]
                 cr, gt_codes = self._coarse_ranks(d, doc_ids[i])
                 self.coarse_log.add((text, d, gt_codes, scores[i].tolist()) if self.nq is None else (text, d, scores[i].tolist()))
-                results.append((text, int(ndoc[i]), cr))
+                results.append((text, int(ndoc[i]) if ndoc is not None else None, cr))
             return self._timed(results, t1 if timing else None)
         if keep:
             qemb = self.nci_query_embedding(decoded, enc_h, mask, dec_h)
@@ -884,7 +899,7 @@ def summarize(results, recall_num, R, both=True, at_all=None):
             found_at_all[0] += len(found) / len(findex)
             found_at_all[1] += 1 / (best + 1) if best is not None else 0
             found_at_all[2] += len(found) > 0
-        nsamples += length
+        nsamples = None if length is None or nsamples is None else nsamples + length    # None: no clusters (the NCI baseline)
     n = len(queries)
     if at_all and not both:
         for t, v in zip(fine, found_at_all):
@@ -892,7 +907,7 @@ def summarize(results, recall_num, R, both=True, at_all=None):
     for t in fine + coarse:
         for k in t:
             t[k] /= n
-    out = dict(recall=fine[0], mrr=fine[1], hitrate=fine[2], ndoc=nsamples / n, nqueries=n)
+    out = dict(recall=fine[0], mrr=fine[1], hitrate=fine[2], ndoc=None if nsamples is None else nsamples / n, nqueries=n)
     if both:
         out.update(cluster_recall=coarse[0], cluster_mrr=coarse[1], cluster_hitrate=coarse[2])
     return out
@@ -905,7 +920,8 @@ def write_metrics(out, metric_path, R, npqclus):
     for name in ("cluster_recall", "cluster_hitrate"):
         if name in out:
             lines += [f"{name}{k} {v}" for k, v in out[name].items()]
-    lines.append(f"ndocs@cluster{R}: {out['ndoc']}")
+    if out["ndoc"] is not None:      # `if args.document_encoder` (main_models.py:4391)
+        lines.append(f"ndocs@cluster{R}: {out['ndoc']}")
     print(f"npqclus: {npqclus}")
     print("\n".join(lines))
     if metric_path:

@@ -25,10 +25,13 @@ from .t5 import GRAPH_MAX_ROWS, DecoderStack, EncoderStack, GraphCache, T5Dims, 
 
 
 class NCIConfig(T5Dims):
-    def __init__(self, M=4, K=32, adaptor_layer_num=4, num_decoder_layers=6, **kw):
+    def __init__(self, M=4, K=32, adaptor_layer_num=4, num_decoder_layers=6, decode_vocab_size=None, **kw):
         super().__init__(num_decoder_layers=num_decoder_layers, **kw)
         self.M, self.K, self.adaptor_layers = M, K, adaptor_layer_num
         self.V = K * (M + 2) + 2            # decode_vocab_size (main_models.py:1337-1339)
+        if decode_vocab_size is not None:   # a checkpoint with a larger decode vocabulary: tokens 2 + p*K + c keep their rows
+            assert decode_vocab_size >= self.V
+            self.V = decode_vocab_size
         self.T = M + 1                      # decoder positions actually evaluated (tokens 0..M)
 
 
@@ -596,8 +599,8 @@ class NCIModel:
         assert max_length in (None, T), "max_length must be the model's M + 2"
         assert tree.K == c.K and tree.depth <= c.M + 1 and len(tree.mask) >= c.M + 1, \
             "decode_tree: a RaggedPrefixTree of this model's K with levels=M + 1 and at most M + 1 codes per id"
-        assert 1 <= R <= 32 and c.K <= 256, "the variable-depth beam step takes R <= 32 beams and K <= 256 codes"
-        assert c.M + 1 <= 8, "variable-depth search: at most 8 decoder positions (the indexed K|V cache)"
+        assert 1 <= R <= ops.VAR_MAX_BEAMS and c.K <= 256, "the variable-depth beam step takes R <= 128 beams and K <= 256 codes"
+        assert c.M + 1 <= 16, "variable-depth search: at most 16 decoder positions (the indexed K|V cache)"
         ids = input_ids.to(self.dev, torch.int64).contiguous()
         mask = attention_mask.to(self.dev, torch.int64).contiguous()
         key = (T, float(length_penalty))
@@ -617,7 +620,8 @@ class NCIModel:
 
     def _search_var(self, ids, mask, R, len_pow, pack, tree):
         """The device part of the variable-depth search: all R beams from the first step (beams 1..R-1 seeded with -1e9,
-        generation_utils.py:745-750), M + 1 steps of mevi_beam_step_var_f32, then mevi_beam_finalize_var_f32."""
+        generation_utils.py:745-750), M + 1 steps of mevi_beam_step_var_f32, then mevi_beam_finalize_var_f32 (R > 32: their
+        _wide forms)."""
         c = self.cfg
         B, K, T = ids.shape[0], c.K, c.M + 2
         enc = self.encoder.forward(self.shared, ids, mask, pack=None if pack else False)

@@ -580,7 +580,7 @@ def attention(q, k, v, heads, out=None, kv_div=1, bias=None, q_pos0=0, key_mask=
 @hip.on_device
 def attention_cached(q, k, v, key_rows, heads, bias=None, q_pos0=0, causal=True, scale=1.0, out=None, split_bound=None):
     """One decode step over ancestor-indexed caches: q [n, H*dh]; k / v [rows, T, H*dh] views of the caches (any row / token
-    strides); key_rows i32 [n, tk] (tk <= 8): position j of row b is cache row key_rows[b, j].  Same bits as `attention` on the
+    strides); key_rows i32 [n, tk] (tk <= 16): position j of row b is cache row key_rows[b, j].  Same bits as `attention` on the
     caches physically re-ordered by the beams' parents (generation_utils.py:927-934)."""
     assert q.dim() == 2 and q.stride(1) == 1 and q.is_cuda and q.dtype == torch.float32
     for t in (k, v):
@@ -884,6 +884,10 @@ def query_pool(mode, R, enc=None, mask=None, dec=None, emb_ids=None, emb_table=N
     return out
 
 
+VAR_NARROW_BEAMS = 32      # mevi_beam_step_var_f32 / mevi_beam_finalize_var_f32: one wavefront per query
+VAR_MAX_BEAMS = 128        # mevi_beam_*_var_wide_f32: one workgroup per query
+
+
 class VarBeamPool:
     """The hypothesis pools of a variable-depth search (BeamHypotheses of MEVI/transformers/generation_utils.py:1268-1315,
     one of R slots per query) and the host-made table len ** length_penalty the kernels divide by (the reference divides
@@ -929,13 +933,15 @@ def beam_step_var(logits, beam_scores, node, prefix, anc, K, p, tree_mask, tree_
     parent, code, child = (torch.empty((nq, R), dtype=torch.int32, device=dev) for _ in range(3))
     out_prefix = torch.empty_like(prefix)
     out_anc = None if anc is None else torch.empty((nq * R, p + 1), dtype=torch.int32, device=dev)
-    st = hip.lib().mevi_beam_step_var_f32(
+    wide = R > VAR_NARROW_BEAMS       # 33 .. 128 beams: the workgroup-per-query pair (same contract, same bits)
+    name = "mevi_beam_step_var_wide_f32" if wide else "mevi_beam_step_var_f32"
+    st = getattr(hip.lib(), name)(
         hip.ptr(logits), hip.ptr(beam_scores), hip.ptr(node), hip.ptr(prefix), None if anc is None or p == 0 else hip.ptr(anc),
         nq, R, K, p, T, hip.ptr(tree_mask) if n_nodes else None, hip.ptr(tree_base) if n_nodes else None,
         hip.ptr(tree_ends) if n_nodes else None, n_nodes, hip.ptr(pool.len_pow), hip.ptr(pool.score), hip.ptr(pool.seq),
         hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), hip.ptr(sc), hip.ptr(parent), hip.ptr(code), hip.ptr(child),
         hip.ptr(out_prefix), None if out_anc is None else hip.ptr(out_anc), hip.stream_ptr())
-    hip.check(st, "mevi_beam_step_var_f32")
+    hip.check(st, name)
     return sc, parent, code, child, out_prefix, out_anc
 
 
@@ -951,9 +957,9 @@ def beam_finalize_var(beam_scores, prefix, pool):
     decoded = torch.empty((nq * R, T), dtype=torch.int64, device=dev)
     scores = torch.empty(nq * R, dtype=torch.float64, device=dev)
     lengths = torch.empty(nq * R, dtype=torch.int32, device=dev)
-    st = hip.lib().mevi_beam_finalize_var_f32(hip.ptr(beam_scores), hip.ptr(prefix), nq, R, T, hip.ptr(pool.len_pow),
-                                              hip.ptr(pool.score), hip.ptr(pool.seq), hip.ptr(pool.len), hip.ptr(pool.tok),
-                                              hip.ptr(pool.state), hip.ptr(decoded), hip.ptr(scores), hip.ptr(lengths),
-                                              hip.stream_ptr())
-    hip.check(st, "mevi_beam_finalize_var_f32")
+    name = "mevi_beam_finalize_var_wide_f32" if R > VAR_NARROW_BEAMS else "mevi_beam_finalize_var_f32"
+    st = getattr(hip.lib(), name)(hip.ptr(beam_scores), hip.ptr(prefix), nq, R, T, hip.ptr(pool.len_pow), hip.ptr(pool.score),
+                                  hip.ptr(pool.seq), hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), hip.ptr(decoded),
+                                  hip.ptr(scores), hip.ptr(lengths), hip.stream_ptr())
+    hip.check(st, name)
     return decoded, scores, lengths

@@ -4,7 +4,11 @@ shapes of the NCI beam search: n = queries x beams rows, 12 heads x 64, tk = 1 .
 
     python tools/bench_attn_cached.py            # runs itself once per kernel form and compares output hashes + times
 
-MEVI_ATTN_FEW_KEYS=direct is the per-lane row walk (rounds 1-2), the default the LDS-transposed form (round 3)."""
+MEVI_ATTN_FEW_KEYS=direct is the per-lane row walk (rounds 1-2), the default the LDS-transposed form (round 3).
+
+    WIDE_KEYS=1 python tools/bench_attn_cached.py     # tk = 9, 12, 16: the indexed kernels against the only alternative there
+                                                      # was before them -- a re-ordered copy of the caches + ops.attention
+(HEADS=12 DH=64: the matrix-core kernel fed through key_rows; HEADS=8 DH=96: the 16-lane-group chains.)"""
 import hashlib
 import json
 import os
@@ -56,7 +60,54 @@ def child():
     print("ATTN_JSON " + json.dumps(out), flush=True)
 
 
+def wide():
+    """tk = 9, 12, 16 (variable-depth search over ids of up to 15 codes): ops.attention_cached against gather + ops.attention."""
+    import torch
+
+    from mevi_amd import ops
+
+    dev = torch.device("cuda", 0)
+    nq, R, T = int(os.environ.get("NQ", "512")), int(os.environ.get("BEAMS", "100")), 16
+    H, dh = int(os.environ.get("HEADS", "12")), int(os.environ.get("DH", "64"))
+    n = int(os.environ.get("NROWS", nq * R))
+    g = torch.Generator(device="cpu").manual_seed(5)
+    gd = torch.Generator(device=dev).manual_seed(5)
+    cache = torch.randn((n, T, 2 * H * dh), generator=gd, device=dev)
+    q = torch.randn((n, H * dh), generator=gd, device=dev)
+    bias = torch.randn((H, T, T), generator=gd, device=dev)
+    ok = True
+    for tk in (9, 12, 16):
+        anc = torch.stack([torch.randint(0, min(R, 1 + 3 * jj), (n,), generator=g, dtype=torch.int32) for jj in range(tk)], 1)
+        key_rows = anc + (torch.arange(n, dtype=torch.int32) // R * R)[:, None]
+        key_rows[:, tk - 1] = torch.arange(n, dtype=torch.int32)
+        key_rows = key_rows.clamp_(max=n - 1).to(dev).contiguous()
+        k, v = cache[:, :, :H * dh], cache[:, :, H * dh:]
+        kw = dict(bias=bias, q_pos0=tk - 1, causal=True, scale=dh ** -0.5 if dh != 64 else 1.0)
+        ar = torch.arange(tk, device=dev)[None, :]
+
+        def copy_then_attend():
+            gathered = cache[key_rows.long(), ar, :]
+            return ops.attention(q.view(n, 1, -1), gathered[:, :, :H * dh], gathered[:, :, H * dh:], H, **kw).view(n, -1)
+
+        ms, outs = {}, {}
+        for name, f in (("indexed", lambda: ops.attention_cached(q, k, v, key_rows, H, **kw)), ("copy+attention", copy_then_attend)):
+            outs[name] = f()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(10):
+                f()
+            torch.cuda.synchronize()
+            ms[name] = (time.perf_counter() - t) / 10 * 1e3
+        same = bool(torch.equal(outs["indexed"], outs["copy+attention"]))
+        ok = ok and same
+        print(f"tk={tk} rows={n} heads={H}x{dh}: indexed {ms['indexed']:.3f} ms, copy + attention {ms['copy+attention']:.3f} ms, "
+              f"same bits: {same}", flush=True)
+    sys.exit(0 if ok else 1)
+
+
 if __name__ == "__main__":
+    if os.environ.get("WIDE_KEYS") == "1":
+        wide()
     if os.environ.get("ATTN_CHILD") == "1":
         child()
         sys.exit(0)

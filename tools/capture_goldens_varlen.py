@@ -7,12 +7,15 @@ Imports the read-only reference through tools/ref_import.py (build container onl
 tests/golden/g1v_*.npz: the id paths, the inputs, `decoded`, `scores`, every step's last-position logits, and the name
 of the G1 / G1T golden that holds the same model's weights (checked equal here).
 
-  python tools/capture_goldens_varlen.py
+  python tools/capture_goldens_varlen.py [case name ...]
 
 Trees: (a) depths 1 .. M + 1 mixed (M + 1 codes leave no room for eos: such hypotheses come from the final flush),
 (b) ids that are prefixes of other ids (eos beside children), (c) a narrow tree whose nodes have fewer than R live
 continuations, so the -1e9-seeded beams and -inf candidates are carried, (d) short ids that fill and close the pools
-before the last step (the reference then stops early: the steps it never ran are not recorded).  Only hypotheses with a finite score are
+before the last step (the reference then stops early: the steps it never ran are not recorded), (e) the pure-NCI shapes
+(`wide`): 40 beams over ids of 2 .. 8 codes (nine decoder positions, ids that are prefixes of ids) and 100 beams over K = 30.
+The wide cases borrow the weights of a G1 model whose decode vocabulary is large enough and set the model's per-position
+code count (`output_vocab_size`, read at every forward: modeling_t5.py:1585) to their own K.  Only hypotheses with a finite score are
 specified by the reference (ties among -inf candidates are torch.topk's choice): every case must return finite scores.
 """
 import json
@@ -62,11 +65,37 @@ def _ids_shallow(rng, M, K):
     return sorted({(c,) for c in range(K)} | {(5, 9, 9), (6, 1)})
 
 
+def _ids_wide_deep(rng, M, K):
+    """(e) 260 ids of 2 .. M codes over all K codes at the first two levels and a few below, every id's prefix of 2+ codes
+    an id with probability 1/4."""
+    out = set()
+    while len(out) < 260:
+        n = int(rng.integers(2, M + 1))
+        full = tuple(int(c) for c in rng.integers(0, K, size=2)) + tuple(int(c) for c in rng.integers(0, min(K, 3), size=n - 2))
+        out.add(full)
+        for m in range(2, n):
+            if rng.random() < 0.25:
+                out.add(full[:m])
+    return sorted(out)
+
+
+def _ids_wide_flat(rng, M, K):
+    """(e) 700 ids of 1 .. M + 1 codes, the first code over all K."""
+    out = set()
+    while len(out) < 700:
+        n = int(rng.integers(1, M + 2))
+        out.add((int(rng.integers(0, K)),) + tuple(int(c) for c in rng.integers(0, min(K, 5), size=n - 1)))
+    return sorted(out)
+
+
 CASES = [  # name, (M, K, beams, model seed, golden with the weights), id maker, queries
     ("mixed", (4, 32, 10, 0, "g1_nci_M4_K32_R10.npz"), _ids_mixed, 3),
     ("prefixes", (3, 16, 4, 1, "g1_nci_M3_K16_R4.npz"), _ids_prefixes, 4),
     ("narrow", (3, 8, 10, 22, "g1t_nci_tree_M3_K8_R10_P30.npz"), _ids_narrow, 4),
     ("shallow", (3, 16, 4, 1, "g1_nci_M3_K16_R4.npz"), _ids_shallow, 4),
+    # wide: (..., (M, K) the borrowed model was built with) -- K (M + 2) + 2 decode tokens must fit its vocabulary
+    ("wide", (8, 8, 40, 1, "g1_nci_M3_K16_R4.npz"), _ids_wide_deep, 3, (3, 16)),
+    ("wide", (4, 30, 100, 0, "g1_nci_M4_K32_R10.npz"), _ids_wide_flat, 2, (4, 32)),
 ]
 
 
@@ -76,8 +105,14 @@ def main():
     from transformers import T5Config, T5ForConditionalGeneration
     from main_models import TreeBuilder, encode_single_newid
 
-    for name, (M, K, beams, seed, weights_from), make_ids, nq in CASES:
-        cfg, model = _model(T5Config, T5ForConditionalGeneration, torch, M, K, seed)
+    only = sys.argv[1:]
+    for name, (M, K, beams, seed, weights_from), make_ids, nq, *borrowed in CASES:
+        if only and name not in only:
+            continue
+        Mm, Km = borrowed[0] if borrowed else (M, K)
+        cfg, model = _model(T5Config, T5ForConditionalGeneration, torch, Mm, Km, seed)
+        assert K * (M + 2) + 2 <= cfg.decode_vocab_size
+        model.output_vocab_size = K
         base = np.load(os.path.join(GOLD, weights_from))
         sd = {k_: v_.detach().numpy() for k_, v_ in model.state_dict().items()}
         assert all(np.array_equal(v_, base["w." + k_]) for k_, v_ in sd.items()), weights_from
@@ -118,7 +153,8 @@ def main():
             scores=scores, paths_flat=np.array([c for pth in paths for c in pth], np.int32),
             paths_len=np.array([len(pth) for pth in paths], np.int32),
             **{f"step{t}_logits": step_logits[t].numpy() for t in range(steps)}, weights_from=np.array(weights_from),
-            cfg=np.array(json.dumps(dict(M=M, K=K, beams=beams, d_model=cfg.d_model, d_ff=cfg.d_ff, num_heads=cfg.num_heads,
+            cfg=np.array(json.dumps(dict(M=M, K=K, beams=beams, **(dict(decode_vocab_size=cfg.decode_vocab_size) if borrowed else {}),
+                                         d_model=cfg.d_model, d_ff=cfg.d_ff, num_heads=cfg.num_heads,
                                          d_kv=cfg.d_kv, num_layers=cfg.num_layers, num_decoder_layers=cfg.num_decoder_layers,
                                          adaptor_layer_num=cfg.adaptor_layer_num, vocab_size=cfg.vocab_size,
                                          layer_norm_epsilon=cfg.layer_norm_epsilon,

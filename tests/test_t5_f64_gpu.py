@@ -28,6 +28,7 @@ import pytest
 import torch
 
 import t5_ref64 as r64
+from f64_bar import check, refs      # the bar above and the (ref64, ref32) cache, shared with tests/test_bert_f64_gpu.py
 from mevi_amd import ops, t5
 
 pytestmark = pytest.mark.gpu
@@ -99,28 +100,6 @@ def batch(lengths, S, seed, holes=False):
         mask[:, 1] = 0
         mask[0, 2] = 0
     return torch.from_numpy(ids), torch.from_numpy(mask)
-
-
-def check(name, hip, ref64, ref32, valid, record_property, factor=4.0):
-    """The per-block bar of the module docstring over the rows / positions `valid` (bool, None: all)."""
-    hip, ref64, ref32 = hip.double().cpu(), ref64.double().cpu(), ref32.double().cpu()
-    if valid is not None:
-        hip, ref64, ref32 = hip[valid], ref64[valid], ref32[valid]
-    assert torch.isfinite(hip).all(), name
-    e_hip = (hip - ref64).abs().max().item()
-    e_32 = (ref32 - ref64).abs().max().item()
-    bar = factor * e_32 + 2.0 ** -22 * ref64.abs().max().item()
-    record_property(name, {"e_hip": e_hip, "e_32": e_32, "bar": bar, "max_ref": ref64.abs().max().item()})
-    print(f"{name}: e_hip {e_hip:.3e}  e_32 {e_32:.3e}  bar {bar:.3e}  max {ref64.abs().max().item():.3e}")
-    assert e_hip <= bar, (name, e_hip, e_32, bar)
-    return e_hip, e_32
-
-
-def refs(key, fn):
-    """(ref64 on the GPU, ref32 on the host) of fn(W, dtype, device): cached across the two norm paths."""
-    if key not in _CACHE:
-        _CACHE[key] = (fn(torch.float64, "cuda"), fn(torch.float32, "cpu"))
-    return _CACHE[key]
 
 
 @pytest.fixture(params=[False, True], ids=["default", "folded"])

@@ -447,7 +447,10 @@ int mevi_beam_step_tree_f32(const float *logits, const float *beam_scores, int64
  * out_anc i32 [nq*R, p+1] (anc of the parent, then the parent's row).  The pool -- pool_score f64 [nq, R], pool_seq /
  * pool_len i32 [nq, R], pool_tok i32 [nq, R, T], pool_state i32 [nq, 4] = (entries, insertions, done, 0), all zero before
  * step 0 -- is updated in place; done |= pool full and worst >= best candidate / len_pow[p+1]; a done query's pool is
- * left alone while its beams keep flowing.  Refused before launch: R > 32, K > 256, T > 64, p + 1 >= T. */
+ * left alone while its beams keep flowing.  One workgroup per query for any 1 <= R <= 128 (pure-NCI eval: 100 beams): the
+ * R*(K+1) candidates in dynamic LDS (129 KiB at R = 128, K = 256; 12 KiB at R = 100, K = 30), 2R rounds of a workgroup-wide
+ * arg-max over the 64-bit (score | index) keys, the walk by a prefix count over the 2R ranks, the pool two slots per lane of
+ * one wavefront.  Refused before launch: R > 128, K > 256, T > 64, p + 1 >= T. */
 int mevi_beam_step_var_f32(const float *logits, const float *beam_scores, const int32_t *node, const int32_t *prefix,
                            const int32_t *anc, int64_t nq, int64_t R, int64_t K, int64_t p, int64_t T,
                            const uint32_t *tree_mask, const int32_t *tree_base, const uint8_t *tree_ends, int64_t n_nodes,
@@ -463,22 +466,6 @@ int mevi_beam_finalize_var_f32(const float *beam_scores, const int32_t *prefix, 
                                const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
                                int32_t *pool_tok, int32_t *pool_state, int64_t *decoded, double *scores, int32_t *lengths,
                                void *stream);
-
-/* The same step and finalize, same arguments and same contract word for word, for up to R <= 128 beams (pure-NCI eval: 100
- * beams): one workgroup per query, the R*(K+1) candidates in dynamic LDS (129 KiB at R = 128, K = 256), 2R rounds of a
- * workgroup-wide arg-max over the 64-bit (score | index) keys, the walk by a prefix count over the 2R ranks, the pool two
- * slots per lane of one wavefront.  For R <= 32 every output and the pool are byte-identical to the narrow pair's.
- * Refused before launch: R > 128, K > 256, T > 64, p + 1 >= T. */
-int mevi_beam_step_var_wide_f32(const float *logits, const float *beam_scores, const int32_t *node, const int32_t *prefix,
-                                const int32_t *anc, int64_t nq, int64_t R, int64_t K, int64_t p, int64_t T,
-                                const uint32_t *tree_mask, const int32_t *tree_base, const uint8_t *tree_ends, int64_t n_nodes,
-                                const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
-                                int32_t *pool_tok, int32_t *pool_state, float *out_scores, int32_t *out_parent,
-                                int32_t *out_code, int32_t *out_node, int32_t *out_prefix, int32_t *out_anc, void *stream);
-int mevi_beam_finalize_var_wide_f32(const float *beam_scores, const int32_t *prefix, int64_t nq, int64_t R, int64_t T,
-                                    const double *len_pow, double *pool_score, int32_t *pool_seq, int32_t *pool_len,
-                                    int32_t *pool_tok, int32_t *pool_state, int64_t *decoded, double *scores,
-                                    int32_t *lengths, void *stream);
 
 /* Row-wise (log-)softmax with the beam step's arithmetic (max, sum of expf(x - max), logf), for the branches that keep
  * EVERY candidate instead of a top-R: mode 0 = log_softmax of x f32 [rows, cols] (the all-paths walk `_generate_all`,

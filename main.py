@@ -267,7 +267,7 @@ def check_semantic_ids(a):
                          "--label_length_cutoff <= 7")
 
 
-PURE_NCI_MAX_BEAMS, PURE_NCI_MAX_CUTOFF = 128, 15     # mevi_beam_step_var_wide_f32; 16 ancestor-indexed decoder positions
+PURE_NCI_MAX_BEAMS, PURE_NCI_MAX_CUTOFF = 128, 15     # mevi_beam_step_var_f32; 16 ancestor-indexed decoder positions
 
 
 def check_pure_nci(a):

@@ -10,8 +10,18 @@
 //                    is strictly better; a non-eos candidate -> the next open beam until R are taken
 //     done |= pool full and worst >= best candidate / cur_len ** length_penalty          (early_stopping = False)
 // A done query's rows keep flowing (the reference pads them); its pool no longer changes.
-// One wavefront per query: R <= 32 beams, K <= 256 codes, the R * (K + 1) candidate scores in LDS, the top-2R one per
-// lane (2R rounds of a wave-wide arg-max over 64-bit (score | index) keys), the walk by ballot, the pool one slot per lane.
+// One WORKGROUP per query, R <= 128 beams (pure-NCI eval runs 100), K <= 256 codes:
+//   * candidates: wave w takes beams w, w + nw, ...; lane l of a row folds columns l, l + 64, ..., then the xor butterfly.
+//     The R * (K + 1) scores live in dynamic LDS: 129 KiB at R = 128, K = 256 (of the CU's 160 KiB; opted into with
+//     hipFuncSetAttribute), one workgroup per CU there, 12 KiB at the pure-NCI shape (R = 100, K = 30);
+//   * top-2R: 2R rounds of a workgroup-wide arg-max over the 64-bit (score | ~index) keys -- keys are distinct, round k takes the
+//     largest key below round k - 1's; wave maxima meet in a double-buffered LDS row, one barrier per round.  Thread t reads
+//     candidates t, t + nt, ...: consecutive banks, no conflicts.  256 threads up to 8192 candidates, 1024 beyond -- the
+//     latency of one query; from 1536 queries on the launch is bound by throughput, and 2R <= 64 ranks run on ONE wave
+//     (the same code with nw = 1: a quarter of the wave slots and barriers that cost nothing);
+//   * walk: rank k on thread k (2R <= 256 = the first four waves), open slot = the count of non-eos ranks below k (ballot
+//     per wave + the four wave totals);
+//   * pool: wave 0 alone, slots j and j + 64 in lane j, the eos candidates of rank < R one after the other in rank order.
 #include "common.h"
 
 #include <math.h>
@@ -19,58 +29,62 @@
 namespace mevi {
 namespace {
 
-constexpr int kVarMaxR = 32, kVarMaxK = 256, kVarMaxT = 64;
+constexpr int kMaxR = 128, kMaxK = 256, kMaxT = 64;
+constexpr int kSmallThreads = 256, kLargeThreads = 1024, kSmallN = 8192;   // both >= 2 * kMaxR: the walk has a thread per rank
+constexpr int kWaveNq = 1536;                                              // queries from which 2R <= 64 ranks take 64 threads
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned int hi = __shfl_xor((unsigned int)(v >> 32), off), lo = __shfl_xor((unsigned int)v, off);
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    v = o > v ? o : v;
-  }
-  return v;
-}
+// Pool of <= 128 slots on one wavefront: slot j in lane j (index 0) and slot 64 + j (index 1).
+struct Pool {
+  double s[2];
+  int seq[2], len[2];
+};
 
 // The pool's worst entry: lowest (score, insertion number), as `sorted([(s, idx) ...])[0]` of BeamHypotheses.add.
-__device__ __forceinline__ void wave_worst(double s, int seq, bool valid, int lane, double &ws, int &wl) {
-  if (!valid) {
-    s = INFINITY;
-    seq = 0x7fffffff;
+__device__ __forceinline__ void wave_worst(const Pool &pl, int count, int lane, double &ws, int &wslot) {
+  double s = INFINITY;
+  int seq = 0x7fffffff, slot = lane;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int j = lane + 64 * i;
+    if (j < count && (pl.s[i] < s || (pl.s[i] == s && pl.seq[i] < seq))) {
+      s = pl.s[i];
+      seq = pl.seq[i];
+      slot = j;
+    }
   }
-  int l = lane;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const double os = __shfl_xor(s, off);
-    const int oq = __shfl_xor(seq, off), ol = __shfl_xor(l, off);
+    const int oq = __shfl_xor(seq, off), ol = __shfl_xor(slot, off);
     if (os < s || (os == s && oq < seq)) {
       s = os;
       seq = oq;
-      l = ol;
+      slot = ol;
     }
   }
   ws = s;
-  wl = l;
+  wslot = slot;
 }
 
-// BeamHypotheses.add for the whole wave: slot j of the pool lives in lane j (ps, pseq, plen; valid iff j < count).
-// Returns the slot the hypothesis went to, or -1.
-__device__ __forceinline__ int pool_add(double sc, int len, int R, int lane, double &ps, int &pseq, int &plen, int &count,
-                                        int &next_seq) {
+// BeamHypotheses.add for the wave.  Returns the slot the hypothesis went to, or -1.
+__device__ __forceinline__ int pool_add(double sc, int len, int R, int lane, Pool &pl, int &count, int &next_seq) {
   int slot;
   if (count < R) {
     slot = count++;
   } else {
     double ws;
     int wl;
-    wave_worst(ps, pseq, lane < count, lane, ws, wl);
+    wave_worst(pl, count, lane, ws, wl);
     if (!(sc > ws)) return -1;
     slot = wl;
   }
-  if (lane == slot) {
-    ps = sc;
-    pseq = next_seq;
-    plen = len;
-  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    if (lane + 64 * i == slot) {
+      pl.s[i] = sc;
+      pl.seq[i] = next_seq;
+      pl.len[i] = len;
+    }
   ++next_seq;
   return slot;
 }
@@ -83,21 +97,48 @@ struct PoolRefs {
   int *state;      // [nq, 4]  count, next insertion number, done, unused
 };
 
-__global__ __launch_bounds__(64) void beam_step_var_kernel(const float *__restrict__ logits, const float *__restrict__ beam_scores,
-                                                          const int *__restrict__ node, const int *__restrict__ prefix,
-                                                          const int *__restrict__ anc, int R, int K, int p, int T,
-                                                          const unsigned int *__restrict__ tmask, const int *__restrict__ tbase,
-                                                          const unsigned char *__restrict__ tends, int n_nodes,
-                                                          const double *__restrict__ len_pow, PoolRefs pool,
-                                                          float *__restrict__ out_scores, int *__restrict__ out_parent,
-                                                          int *__restrict__ out_code, int *__restrict__ out_node,
-                                                          int *__restrict__ out_prefix, int *__restrict__ out_anc) {
+__device__ __forceinline__ void pool_load(const PoolRefs &pool, size_t qR, int count, int lane, Pool &pl) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int j = lane + 64 * i;
+    pl.s[i] = 0.0;
+    pl.seq[i] = pl.len[i] = 0;
+    if (j < count) {
+      pl.s[i] = pool.score[qR + j];
+      pl.seq[i] = pool.seq[qR + j];
+      pl.len[i] = pool.len[qR + j];
+    }
+  }
+}
+
+__device__ __forceinline__ void pool_store(const PoolRefs &pool, size_t qR, int count, int lane, const Pool &pl) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int j = lane + 64 * i;
+    if (j < count) {
+      pool.score[qR + j] = pl.s[i];
+      pool.seq[qR + j] = pl.seq[i];
+      pool.len[qR + j] = pl.len[i];
+    }
+  }
+}
+
+__global__ __launch_bounds__(1024) void beam_step_var_kernel(
+    const float *__restrict__ logits, const float *__restrict__ beam_scores, const int *__restrict__ node,
+    const int *__restrict__ prefix, const int *__restrict__ anc, int R, int K, int p, int T,
+    const unsigned int *__restrict__ tmask, const int *__restrict__ tbase, const unsigned char *__restrict__ tends, int n_nodes,
+    const double *__restrict__ len_pow, PoolRefs pool, float *__restrict__ out_scores, int *__restrict__ out_parent,
+    int *__restrict__ out_code, int *__restrict__ out_node, int *__restrict__ out_prefix, int *__restrict__ out_anc) {
   extern __shared__ float sval[];                       // R * (K + 1) candidate scores
-  const int q = blockIdx.x, lane = threadIdx.x;
+  __shared__ unsigned long long top[2 * kMaxR];         // rank k's key
+  __shared__ unsigned long long wmax[2][16];            // the waves' maxima of a round (rounds alternate rows)
+  __shared__ int open_total[4];                         // non-eos ranks per wave of the walk
+  const int q = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
   const int ncol = K + 1, N = R * ncol, W = (K + 31) >> 5;
   const size_t qR = (size_t)q * R;
 
-  for (int r = 0; r < R; ++r) {
+  for (int r = wave; r < R; r += nw) {                  // wave-uniform
     const float *row = logits + (qR + r) * ncol;
     float m = -INFINITY;
     for (int c = lane; c < ncol; c += 64) m = fmaxf(m, row[c]);
@@ -118,28 +159,38 @@ __global__ __launch_bounds__(64) void beam_step_var_kernel(const float *__restri
   }
   __syncthreads();
 
-  // top-2R, rank k in lane k: keys are distinct (the index is part of them), so round k takes the largest key below round k-1's
-  unsigned long long prev = ~0ull, mine = 0ull;
+  unsigned long long prev = ~0ull;
   for (int k = 0; k < 2 * R; ++k) {
     unsigned long long best = 0ull;
-    for (int i = lane; i < N; i += 64) {
+    for (int i = tid; i < N; i += nt) {
       const unsigned long long key = make_key(sval[i], (unsigned int)i);
       if (key < prev && key > best) best = key;
     }
     best = wave_max_u64(best);
-    if (lane == k) mine = best;
+    if (lane == 0) wmax[k & 1][wave] = best;
+    __syncthreads();
+    best = 0ull;
+    for (int w = 0; w < nw; ++w) {
+      const unsigned long long o = wmax[k & 1][w];
+      best = o > best ? o : best;
+    }
+    if (tid == 0) top[k] = best;
     prev = best;
   }
-  const bool act = lane < 2 * R;
+  __syncthreads();
+
+  // the walk: rank = tid (the first four waves hold every rank; all threads reach the barrier)
+  const bool act = tid < 2 * R;
+  const unsigned long long mine = act ? top[tid] : 0ull;
   const float val = key_score(mine);
   const int flat = act ? (int)key_id(mine) : 0;
   const int r = flat / ncol, col = flat - r * ncol;
   const bool is_eos = col == 0;
-  const float best_val = __shfl(val, 0);
-
   const unsigned long long open_mask = __ballot(act && !is_eos);
-  const unsigned long long eos_mask = __ballot(act && is_eos && lane < R);
-  const int slot = __popcll(open_mask & ((1ull << lane) - 1ull));
+  if (wave < 4 && lane == 0) open_total[wave] = __popcll(open_mask);
+  __syncthreads();
+  int slot = __popcll(open_mask & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave && w < 4; ++w) slot += open_total[w];
   if (act && !is_eos && slot < R) {          // at most R of 2R candidates are eos (one per beam): R open beams always exist
     const int code = col - 1, n0 = node[qR + r];
     int child = -1;
@@ -165,36 +216,30 @@ __global__ __launch_bounds__(64) void beam_step_var_kernel(const float *__restri
     }
   }
 
+  if (wave != 0) return;                         // the pool: wave 0 alone (no barrier below)
   int count = pool.state[q * 4 + 0], next_seq = pool.state[q * 4 + 1];
   const int done = pool.state[q * 4 + 2];
   if (done) return;                              // wave-uniform
-  double ps = 0.0;
-  int pseq = 0, plen = 0;
-  if (lane < count) {
-    ps = pool.score[qR + lane];
-    pseq = pool.seq[qR + lane];
-    plen = pool.len[qR + lane];
-  }
+  Pool pl;
+  pool_load(pool, qR, count, lane, pl);
   const double lp = len_pow[p + 1];
-  for (unsigned long long todo = eos_mask; todo; todo &= todo - 1ull) {
-    const int k = __ffsll((long long)todo) - 1;
-    const float v = __shfl(val, k);
-    const int rr = __shfl(r, k);
-    const int s = pool_add((double)v / lp, p + 1, R, lane, ps, pseq, plen, count, next_seq);
+  const float best_val = key_score(top[0]);
+  for (int k = 0; k < R; ++k) {                  // eos candidates of rank < R, in rank order (top[k]: one address, a broadcast)
+    const unsigned long long key = top[k];
+    const int fl = (int)key_id(key);
+    const int rr = fl / ncol;
+    if (fl - rr * ncol != 0) continue;           // wave-uniform
+    const int s = pool_add((double)key_score(key) / lp, p + 1, R, lane, pl, count, next_seq);
     if (s >= 0 && lane < T) pool.tok[(qR + s) * T + lane] = lane <= p ? prefix[(qR + rr) * T + lane] : 0;
   }
   int now_done = 0;
   if (count >= R) {
     double ws;
     int wl;
-    wave_worst(ps, pseq, lane < count, lane, ws, wl);
+    wave_worst(pl, count, lane, ws, wl);
     now_done = ws >= (double)best_val / lp;
   }
-  if (lane < count) {
-    pool.score[qR + lane] = ps;
-    pool.seq[qR + lane] = pseq;
-    pool.len[qR + lane] = plen;
-  }
+  pool_store(pool, qR, count, lane, pl);
   if (lane == 0) {
     pool.state[q * 4 + 0] = count;
     pool.state[q * 4 + 1] = next_seq;
@@ -204,41 +249,49 @@ __global__ __launch_bounds__(64) void beam_step_var_kernel(const float *__restri
 
 // After the last step: queries that are not done add their R open beams (length T, no eos fits), then every pool is
 // written out best first -- `sorted(beams, key=score)` popped from the end: score descending, equal scores latest first.
+// One wavefront per query; the ranks of the output are counted against an LDS copy of the pool.
 __global__ __launch_bounds__(64) void beam_finalize_var_kernel(const float *__restrict__ beam_scores, const int *__restrict__ prefix,
                                                               int R, int T, const double *__restrict__ len_pow, PoolRefs pool,
                                                               int64_t *__restrict__ decoded, double *__restrict__ scores,
                                                               int *__restrict__ lengths) {
+  __shared__ double sps[kMaxR];
+  __shared__ int spq[kMaxR];
   const int q = blockIdx.x, lane = threadIdx.x;
   const size_t qR = (size_t)q * R;
   int count = pool.state[q * 4 + 0], next_seq = pool.state[q * 4 + 1];
   const int done = pool.state[q * 4 + 2];
-  double ps = 0.0;
-  int pseq = 0, plen = 0;
-  if (lane < count) {
-    ps = pool.score[qR + lane];
-    pseq = pool.seq[qR + lane];
-    plen = pool.len[qR + lane];
-  }
+  Pool pl;
+  pool_load(pool, qR, count, lane, pl);
   if (!done) {
     const double lp = len_pow[T];
     for (int i = 0; i < R; ++i) {
-      const int s = pool_add((double)beam_scores[qR + i] / lp, T, R, lane, ps, pseq, plen, count, next_seq);
+      const int s = pool_add((double)beam_scores[qR + i] / lp, T, R, lane, pl, count, next_seq);
       if (s >= 0 && lane < T) pool.tok[(qR + s) * T + lane] = prefix[(qR + i) * T + lane];
     }
   }
-  __syncthreads();                               // the flush's tokens (written by other lanes) before they are read below
-  int rank = 0;
-  for (int i = 0; i < count; ++i) {
-    const double os = __shfl(ps, i);
-    const int oq = __shfl(pseq, i);
-    rank += (os > ps || (os == ps && oq > pseq)) ? 1 : 0;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int j = lane + 64 * i;
+    if (j < count && j < kMaxR) {
+      sps[j] = pl.s[i];
+      spq[j] = pl.seq[i];
+    }
   }
-  if (lane < count && rank < R) {                // count == R here: a done pool is full, a flushed one got R additions
-    const int *src = pool.tok + (qR + lane) * T;
-    int64_t *dst = decoded + (qR + rank) * T;
-    for (int j = 0; j < T; ++j) dst[j] = j < plen ? src[j] : (j == plen ? 1 : 0);
-    scores[qR + rank] = ps;
-    lengths[qR + rank] = plen;
+  __syncthreads();                               // the LDS copy, and the flush's tokens (written by other lanes) before they are read
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int j = lane + 64 * i;
+    if (j >= count) continue;
+    int rank = 0;
+    for (int o = 0; o < count; ++o) rank += (sps[o] > pl.s[i] || (sps[o] == pl.s[i] && spq[o] > pl.seq[i])) ? 1 : 0;
+    if (rank < R) {                              // count == R here: a done pool is full, a flushed one got R additions
+      const int plen = pl.len[i];
+      const int *src = pool.tok + (qR + j) * T;
+      int64_t *dst = decoded + (qR + rank) * T;
+      for (int t = 0; t < T; ++t) dst[t] = t < plen ? src[t] : (t == plen ? 1 : 0);
+      scores[qR + rank] = pl.s[i];
+      lengths[qR + rank] = plen;
+    }
   }
 }
 
@@ -255,10 +308,10 @@ extern "C" int mevi_beam_step_var_f32(const float *logits, const float *beam_sco
                                       int32_t *out_parent, int32_t *out_code, int32_t *out_node, int32_t *out_prefix,
                                       int32_t *out_anc, void *stream) {
   MEVI_REQUIRE(nq >= 0 && R > 0 && K > 0 && p >= 0 && T > 0 && n_nodes >= 0, MEVI_ERR_INVALID_ARG, "beam_step_var: bad shape");
-  MEVI_REQUIRE(R <= kVarMaxR && K <= kVarMaxK, MEVI_ERR_UNSUPPORTED, "beam_step_var: R=%lld, K=%lld beyond R <= %d, K <= %d",
-               (long long)R, (long long)K, kVarMaxR, kVarMaxK);
-  MEVI_REQUIRE(T <= kVarMaxT && p + 1 < T, MEVI_ERR_UNSUPPORTED, "beam_step_var: step p=%lld needs p + 1 < T <= %d (T=%lld)",
-               (long long)p, kVarMaxT, (long long)T);
+  MEVI_REQUIRE(R <= kMaxR && K <= kMaxK, MEVI_ERR_UNSUPPORTED, "beam_step_var: R=%lld, K=%lld beyond R <= %d, K <= %d",
+               (long long)R, (long long)K, kMaxR, kMaxK);
+  MEVI_REQUIRE(T <= kMaxT && p + 1 < T, MEVI_ERR_UNSUPPORTED, "beam_step_var: step p=%lld needs p + 1 < T <= %d (T=%lld)",
+               (long long)p, kMaxT, (long long)T);
   MEVI_REQUIRE(nq * R < (1LL << 31) / (T > K + 1 ? T : K + 1), MEVI_ERR_UNSUPPORTED, "beam_step_var: nq=%lld too large", (long long)nq);
   if (nq == 0) return MEVI_OK;
   MEVI_REQUIRE(logits && beam_scores && node && prefix && len_pow && pool_score && pool_seq && pool_len && pool_tok &&
@@ -267,9 +320,14 @@ extern "C" int mevi_beam_step_var_f32(const float *logits, const float *beam_sco
   MEVI_REQUIRE(n_nodes == 0 || (tree_mask && tree_base && tree_ends), MEVI_ERR_INVALID_ARG, "beam_step_var: null tree level");
   MEVI_REQUIRE(!out_anc || p == 0 || anc, MEVI_ERR_INVALID_ARG, "beam_step_var: out_anc without anc");
   const PoolRefs pool{pool_score, pool_seq, pool_len, pool_tok, pool_state};
-  hipLaunchKernelGGL(beam_step_var_kernel, dim3((unsigned)nq), dim3(64), (size_t)(R * (K + 1)) * sizeof(float), (hipStream_t)stream, logits, beam_scores, node, prefix,
-                     anc, (int)R, (int)K, (int)p, (int)T, tree_mask, tree_base, tree_ends, (int)n_nodes, len_pow, pool, out_scores,
-                     out_parent, out_code, out_node, out_prefix, out_anc);
+  const size_t lds = (size_t)(R * (K + 1)) * sizeof(float);
+  if (lds > 65536)   // dynamic LDS beyond 64 KiB must be opted into
+    MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(beam_step_var_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMaxR * (kMaxK + 1) * (int)sizeof(float)));
+  const int threads = 2 * R <= 64 && nq >= kWaveNq ? 64 : R * (K + 1) <= kSmallN ? kSmallThreads : kLargeThreads;
+  hipLaunchKernelGGL(beam_step_var_kernel, dim3((unsigned)nq), dim3(threads), lds, (hipStream_t)stream, logits, beam_scores, node,
+                     prefix, anc, (int)R, (int)K, (int)p, (int)T, tree_mask, tree_base, tree_ends, (int)n_nodes, len_pow, pool,
+                     out_scores, out_parent, out_code, out_node, out_prefix, out_anc);
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;
 }
@@ -279,8 +337,8 @@ extern "C" int mevi_beam_finalize_var_f32(const float *beam_scores, const int32_
                                           int32_t *pool_tok, int32_t *pool_state, int64_t *decoded, double *scores,
                                           int32_t *lengths, void *stream) {
   MEVI_REQUIRE(nq >= 0 && R > 0 && T > 0, MEVI_ERR_INVALID_ARG, "beam_finalize_var: bad shape");
-  MEVI_REQUIRE(R <= kVarMaxR && T <= kVarMaxT, MEVI_ERR_UNSUPPORTED, "beam_finalize_var: R=%lld, T=%lld beyond R <= %d, T <= %d",
-               (long long)R, (long long)T, kVarMaxR, kVarMaxT);
+  MEVI_REQUIRE(R <= kMaxR && T <= kMaxT, MEVI_ERR_UNSUPPORTED, "beam_finalize_var: R=%lld, T=%lld beyond R <= %d, T <= %d",
+               (long long)R, (long long)T, kMaxR, kMaxT);
   MEVI_REQUIRE(nq * R < (1LL << 31) / T, MEVI_ERR_UNSUPPORTED, "beam_finalize_var: nq=%lld too large", (long long)nq);
   if (nq == 0) return MEVI_OK;
   MEVI_REQUIRE(beam_scores && prefix && len_pow && pool_score && pool_seq && pool_len && pool_tok && pool_state && decoded &&

@@ -59,6 +59,16 @@ __host__ __device__ static inline float key_score(uint64_t key) {
 __host__ __device__ static inline uint32_t key_id(uint64_t key) {
   return 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu);
 }
+// The largest key of a wavefront, in every lane.
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned int hi = __shfl_xor((unsigned int)(v >> 32), off), lo = __shfl_xor((unsigned int)v, off);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    v = o > v ? o : v;
+  }
+  return v;
+}
 
 // One compare-exchange stage of an in-LDS bitonic network over P 64-bit keys, NT threads.  A thread loads
 // the keys of four pairs before it compares and stores them: the LDS round trips of a stage overlap instead

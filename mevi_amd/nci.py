@@ -620,8 +620,8 @@ class NCIModel:
 
     def _search_var(self, ids, mask, R, len_pow, pack, tree):
         """The device part of the variable-depth search: all R beams from the first step (beams 1..R-1 seeded with -1e9,
-        generation_utils.py:745-750), M + 1 steps of mevi_beam_step_var_f32, then mevi_beam_finalize_var_f32 (R > 32: their
-        _wide forms)."""
+        generation_utils.py:745-750), M + 1 steps of mevi_beam_step_var_f32, then mevi_beam_finalize_var_f32 (1 .. 128
+        beams)."""
         c = self.cfg
         B, K, T = ids.shape[0], c.K, c.M + 2
         enc = self.encoder.forward(self.shared, ids, mask, pack=None if pack else False)

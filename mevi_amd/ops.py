@@ -884,8 +884,7 @@ def query_pool(mode, R, enc=None, mask=None, dec=None, emb_ids=None, emb_table=N
     return out
 
 
-VAR_NARROW_BEAMS = 32      # mevi_beam_step_var_f32 / mevi_beam_finalize_var_f32: one wavefront per query
-VAR_MAX_BEAMS = 128        # mevi_beam_*_var_wide_f32: one workgroup per query
+VAR_MAX_BEAMS = 128        # mevi_beam_step_var_f32 / mevi_beam_finalize_var_f32: one workgroup per query, 1 .. 128 beams
 
 
 class VarBeamPool:
@@ -933,15 +932,13 @@ def beam_step_var(logits, beam_scores, node, prefix, anc, K, p, tree_mask, tree_
     parent, code, child = (torch.empty((nq, R), dtype=torch.int32, device=dev) for _ in range(3))
     out_prefix = torch.empty_like(prefix)
     out_anc = None if anc is None else torch.empty((nq * R, p + 1), dtype=torch.int32, device=dev)
-    wide = R > VAR_NARROW_BEAMS       # 33 .. 128 beams: the workgroup-per-query pair (same contract, same bits)
-    name = "mevi_beam_step_var_wide_f32" if wide else "mevi_beam_step_var_f32"
-    st = getattr(hip.lib(), name)(
+    st = hip.lib().mevi_beam_step_var_f32(
         hip.ptr(logits), hip.ptr(beam_scores), hip.ptr(node), hip.ptr(prefix), None if anc is None or p == 0 else hip.ptr(anc),
         nq, R, K, p, T, hip.ptr(tree_mask) if n_nodes else None, hip.ptr(tree_base) if n_nodes else None,
         hip.ptr(tree_ends) if n_nodes else None, n_nodes, hip.ptr(pool.len_pow), hip.ptr(pool.score), hip.ptr(pool.seq),
         hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), hip.ptr(sc), hip.ptr(parent), hip.ptr(code), hip.ptr(child),
         hip.ptr(out_prefix), None if out_anc is None else hip.ptr(out_anc), hip.stream_ptr())
-    hip.check(st, name)
+    hip.check(st, "mevi_beam_step_var_f32")
     return sc, parent, code, child, out_prefix, out_anc
 
 
@@ -957,9 +954,9 @@ def beam_finalize_var(beam_scores, prefix, pool):
     decoded = torch.empty((nq * R, T), dtype=torch.int64, device=dev)
     scores = torch.empty(nq * R, dtype=torch.float64, device=dev)
     lengths = torch.empty(nq * R, dtype=torch.int32, device=dev)
-    name = "mevi_beam_finalize_var_wide_f32" if R > VAR_NARROW_BEAMS else "mevi_beam_finalize_var_f32"
-    st = getattr(hip.lib(), name)(hip.ptr(beam_scores), hip.ptr(prefix), nq, R, T, hip.ptr(pool.len_pow), hip.ptr(pool.score),
-                                  hip.ptr(pool.seq), hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), hip.ptr(decoded),
-                                  hip.ptr(scores), hip.ptr(lengths), hip.stream_ptr())
-    hip.check(st, name)
+    st = hip.lib().mevi_beam_finalize_var_f32(
+        hip.ptr(beam_scores), hip.ptr(prefix), nq, R, T, hip.ptr(pool.len_pow), hip.ptr(pool.score), hip.ptr(pool.seq),
+        hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), hip.ptr(decoded), hip.ptr(scores), hip.ptr(lengths),
+        hip.stream_ptr())
+    hip.check(st, "mevi_beam_finalize_var_f32")
     return decoded, scores, lengths

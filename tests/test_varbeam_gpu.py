@@ -21,10 +21,40 @@ def random_ids(rng, K, depth, n, spread):
     return sorted(out)
 
 
-def run_both(cuda, rng, R, K, T, B, paths, quantum=None, lp=0.8, check_steps=True):
-    """T - 1 steps on random logits through the kernel and the restatement, compared after every step and at the end."""
+def step_direct(logits, scores, node, prefix, anc, K, p, mask, base, ends, pool):
+    """ops.beam_step_var's call on the C entry point itself: raw pointers, fresh outputs, anc null at p = 0."""
+    from mevi_amd import hip
+
+    (B, R), T, dev = scores.shape, pool.T, scores.device
+    i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)                        # noqa: E731
+    out = (torch.empty((B, R), dtype=torch.float32, device=dev), i32(B, R), i32(B, R), i32(B, R), i32(B, R, T), i32(B * R, p + 1))
+    st = hip.lib().mevi_beam_step_var_f32(
+        hip.ptr(logits), hip.ptr(scores), hip.ptr(node), hip.ptr(prefix), hip.ptr(anc) if p else None, B, R, K, p, T, hip.ptr(mask),
+        hip.ptr(base), hip.ptr(ends), base.numel(), hip.ptr(pool.len_pow), hip.ptr(pool.score), hip.ptr(pool.seq),
+        hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), *(hip.ptr(t) for t in out), hip.stream_ptr())
+    hip.check(st, "mevi_beam_step_var_f32")
+    return out
+
+
+def finalize_direct(scores, prefix, pool):
+    from mevi_amd import hip
+
+    (B, R), T, dev = scores.shape, pool.T, scores.device
+    out = (torch.empty((B * R, T), dtype=torch.int64, device=dev), torch.empty(B * R, dtype=torch.float64, device=dev),
+           torch.zeros(B * R, dtype=torch.int32, device=dev))
+    st = hip.lib().mevi_beam_finalize_var_f32(
+        hip.ptr(scores), hip.ptr(prefix), B, R, T, hip.ptr(pool.len_pow), hip.ptr(pool.score), hip.ptr(pool.seq),
+        hip.ptr(pool.len), hip.ptr(pool.tok), hip.ptr(pool.state), *(hip.ptr(t) for t in out), hip.stream_ptr())
+    hip.check(st, "mevi_beam_finalize_var_f32")
+    return out
+
+
+def run_both(cuda, rng, R, K, T, B, paths, quantum=None, lp=0.8, check_steps=True, direct=False):
+    """T - 1 steps on random logits through the kernel (ops.beam_step_var; `direct`: the C entry points themselves) and the
+    restatement, compared after every step and at the end."""
     from mevi_amd import nci, ops
 
+    step, finalize = (step_direct, finalize_direct) if direct else (ops.beam_step_var, ops.beam_finalize_var)
     tree = nci.RaggedPrefixTree(paths, K, cuda, levels=T - 1)
     root = vr.build_trie(paths)
     vr.trie_levels(root, K, T - 1)                                   # numbers every node within its level
@@ -43,8 +73,8 @@ def run_both(cuda, rng, R, K, T, B, paths, quantum=None, lp=0.8, check_steps=Tru
         logits = torch.from_numpy(logits.astype(np.float32)).to(cuda)
         lsm = ops.row_softmax(logits, log=True).cpu().numpy().reshape(B, R, K + 1)
         key_rows = torch.cat([anc, torch.arange(B * R, dtype=torch.int32, device=cuda)[:, None]], 1)
-        scores, parent, code, node, prefix, anc = ops.beam_step_var(logits, scores, node, prefix, anc, K, p, tree.mask[p],
-                                                                    tree.base[p], tree.ends[p], pool)
+        scores, parent, code, node, prefix, anc = step(logits, scores, node, prefix, anc, K, p, tree.mask[p], tree.base[p],
+                                                       tree.ends[p], pool)
         for b, q in enumerate(qs):
             q.step(p, lsm[b])
         if not check_steps:
@@ -52,18 +82,18 @@ def run_both(cuda, rng, R, K, T, B, paths, quantum=None, lp=0.8, check_steps=Tru
         sc, par, cod, nod, pre = (t.cpu().numpy() for t in (scores, parent, code, node, prefix))
         rows = (torch.arange(B, device=cuda)[:, None] * R + parent.long()).reshape(-1)
         assert torch.equal(anc, key_rows[rows])
-        state = pool.state.cpu().numpy()
+        state, ps, pseq, plen, ptok = (t.cpu().numpy() for t in (pool.state, pool.score, pool.seq, pool.len, pool.tok))
         for b, q in enumerate(qs):
             assert np.array_equal(sc[b].view(np.uint32), q.scores.astype(np.float32).view(np.uint32)), (p, b, "scores")
             assert par[b].tolist() == q.parent and cod[b].tolist() == q.code, (p, b)
             assert [row[:p + 2].tolist() for row in pre[b]] == q.prefix and not pre[b][:, p + 2:].any()
             assert nod[b].tolist() == [-1 if nd is None else nd.index for nd in q.nodes], (p, b, "child node")
             assert state[b, 0] == len(q.pool.beams) and state[b, 1] == q.pool.inserted and bool(state[b, 2]) == q.done, (p, b)
-            ps, pseq = pool.score[b].cpu().numpy(), pool.seq[b].cpu().numpy()
-            got = sorted(zip(pseq[:state[b, 0]].tolist(), ps[:state[b, 0]].tolist()))
-            assert got == sorted((h[1], h[0]) for h in q.pool.beams), (p, b, "pool")
+            # the live entries by insertion number: score, token count, the tokens and zeros after them up to T
+            got = sorted((int(pseq[b, j]), float(ps[b, j]), int(plen[b, j]), ptok[b, j].tolist()) for j in range(state[b, 0]))
+            assert got == sorted((h[1], h[0], len(h[2]), h[2] + [0] * (T - len(h[2]))) for h in q.pool.beams), (p, b, "pool")
         done_seen.append(state[:, 2].copy())
-    decoded, hyp, lengths = ops.beam_finalize_var(scores, prefix, pool)
+    decoded, hyp, lengths = finalize(scores, prefix, pool)
     decoded, hyp, lengths = decoded.cpu().numpy(), hyp.cpu().numpy(), lengths.cpu().numpy()
     for b, q in enumerate(qs):
         d, s, l = q.finalize()
@@ -108,6 +138,35 @@ def test_all_eos_rows_done_queries_and_both_length_limits(cuda):
     qs, done_seen, lengths = run_both(cuda, rng, R, K, T, 24, mix)
     flags = [q.done for q in qs]
     assert any(flags) and not all(flags) and lengths.min() == 2
+
+
+@pytest.mark.parametrize("R", [1, 10, 32])
+def test_many_queries_on_one_wave_each_give_the_bits_of_the_workgroup_launch(cuda, R):
+    """From 1536 queries on, 2R <= 64 ranks run on 64 threads: six queries repeated 256 times give, in every copy, the bytes
+    the six give alone (the 256-thread launch, which the other tests hold to the restatement).  Half-integer logits."""
+    from mevi_amd import nci, ops
+
+    rng = np.random.default_rng(90 + R)
+    K, T, B, copies = 30, 6, 6, 256
+    tree = nci.RaggedPrefixTree([(c,) for c in range(K)] + random_ids(rng, K, 4, 40, 3), K, cuda, levels=T - 1)
+    logits = [torch.from_numpy((np.round(rng.standard_normal((B * R, K + 1)) * 4) / 2).astype(np.float32)).to(cuda)
+              for _ in range(T - 1)]
+
+    def search(n):
+        pool = ops.VarBeamPool(B * n, R, T, 0.8, cuda)
+        scores = torch.zeros((B * n, R), dtype=torch.float32, device=cuda)
+        scores[:, 1:] = -1e9
+        node = torch.zeros((B * n, R), dtype=torch.int32, device=cuda)
+        prefix, anc, seen = torch.zeros((B * n, R, T), dtype=torch.int32, device=cuda), None, []
+        for p in range(T - 1):
+            out = step_direct(logits[p].repeat(n, 1), scores, node, prefix, anc, K, p, tree.mask[p], tree.base[p], tree.ends[p], pool)
+            scores, _, _, node, prefix, anc = out
+            rows = (anc.view(n, B * R, p + 1) - torch.arange(n, device=cuda, dtype=torch.int32)[:, None, None] * (B * R))
+            seen += list(out[:5]) + [rows] + [t.clone() for t in (pool.score, pool.seq, pool.len, pool.tok, pool.state)]
+        return seen + list(finalize_direct(scores, prefix, pool))
+
+    for i, (a, b) in enumerate(zip(search(1), search(copies))):
+        assert torch.equal(b.reshape(copies, *a.shape), a.reshape(1, *a.shape).expand(copies, *a.shape)), i
 
 
 def test_unsupported_shapes_are_refused_before_launch(cuda):

@@ -1,8 +1,7 @@
-"""The variable-depth beam search beyond 32 beams (mevi_beam_step_var_wide_f32 / mevi_beam_finalize_var_wide_f32, R <= 128)
-and the ancestor-indexed attention over 9 .. 16 cached keys: the kernels against the restatement tests/varbeam_ref.py bit
-for bit (the `run_both` of test_varbeam_gpu.py: ops.beam_step_var sends R > 32 to the wide pair), the wide pair against the
-narrow pair on the shapes both take, refusals before launch, and NCIModel.generate against the reference's goldens
-g1v_wide_* (40 beams over ids of 2 .. 8 codes: nine decoder positions; 100 beams over K = 30)."""
+"""The variable-depth beam search at 33 .. 128 beams (the 1024-thread form and the opted-in LDS included) and the
+ancestor-indexed attention over 9 .. 16 cached keys: the kernels against the restatement tests/varbeam_ref.py bit for bit (the
+`run_both` of test_varbeam_gpu.py), the C entry points driven directly, refusals before launch, and NCIModel.generate against
+the reference's goldens g1v_wide_* (40 beams over ids of 2 .. 8 codes: nine decoder positions; 100 beams over K = 30)."""
 import os
 
 import numpy as np
@@ -61,52 +60,14 @@ def test_wide_pools_fill_close_and_flush(cuda):
     assert all(np.isinf(q.scores).any() for q in qs)               # open beams taken from -inf candidates
 
 
-def _search_direct(cuda, suffix, seed, R, K, T, B, paths):
-    """T - 1 steps and the finalize through the entry points `mevi_beam_{step,finalize}_var<suffix>_f32` themselves, on seeded
-    logits -> every tensor the kernels wrote, as bytes."""
-    from mevi_amd import hip, nci
-
-    L = hip.lib()
-    step, fin = getattr(L, f"mevi_beam_step_var{suffix}_f32"), getattr(L, f"mevi_beam_finalize_var{suffix}_f32")
-    rng = np.random.default_rng(seed)
-    tree = nci.RaggedPrefixTree(paths, K, cuda, levels=T - 1)
-    i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=cuda)                       # noqa: E731
-    len_pow = torch.tensor([float(l) ** 0.8 for l in range(T + 1)], dtype=torch.float64).to(cuda)
-    pool = (torch.zeros((B, R), dtype=torch.float64, device=cuda), i32(B, R), i32(B, R), i32(B, R, T), i32(B, 4))
-    scores = torch.zeros((B, R), dtype=torch.float32, device=cuda)
-    scores[:, 1:] = -1e9
-    node, prefix, anc = i32(B, R), i32(B, R, T), i32(B * R, 0)
-    seen = []
-    for p in range(T - 1):
-        logits = torch.from_numpy((np.round(rng.standard_normal((B * R, K + 1)) * 4) / 2).astype(np.float32)).to(cuda)
-        out = (torch.empty((B, R), dtype=torch.float32, device=cuda), i32(B, R), i32(B, R), i32(B, R), i32(B, R, T),
-               i32(B * R, p + 1))
-        n = tree.base[p].numel()
-        st = step(hip.ptr(logits), hip.ptr(scores), hip.ptr(node), hip.ptr(prefix), hip.ptr(anc) if p else None, B, R, K, p, T,
-                  hip.ptr(tree.mask[p]), hip.ptr(tree.base[p]), hip.ptr(tree.ends[p]), n, hip.ptr(len_pow),
-                  *(hip.ptr(t) for t in pool), *(hip.ptr(t) for t in out), hip.stream_ptr())
-        hip.check(st, "step" + suffix)
-        scores, _, _, node, prefix, anc = out
-        seen += [t.cpu().numpy().tobytes() for t in out] + [t.cpu().numpy().tobytes() for t in pool[:3] + pool[4:]]
-    decoded = torch.empty((B * R, T), dtype=torch.int64, device=cuda)
-    hyp = torch.empty(B * R, dtype=torch.float64, device=cuda)
-    lengths = i32(B * R)
-    st = fin(hip.ptr(scores), hip.ptr(prefix), B, R, T, hip.ptr(len_pow), *(hip.ptr(t) for t in pool), hip.ptr(decoded),
-             hip.ptr(hyp), hip.ptr(lengths), hip.stream_ptr())
-    hip.check(st, "finalize" + suffix)
-    return seen + [t.cpu().numpy().tobytes() for t in (decoded, hyp, lengths) + pool]
-
-
 @pytest.mark.parametrize("R", [1, 10, 32])
-def test_wide_entry_points_equal_the_narrow_ones_up_to_32_beams(cuda, R):
-    """Same inputs (half-integer logits: ties included) through both pairs: every output of every step, the pool (scores,
-    insertion numbers, lengths, state; its tokens after finalize) and the hypotheses are byte-identical."""
+def test_entry_points_match_restatement_up_to_32_beams(cuda, R):
+    """The C entry points themselves (raw pointers, anc null at p = 0) on half-integer logits (ties included): every output
+    of every step, the pool (scores, insertion numbers, lengths, tokens, state) and the hypotheses against the restatement."""
     rng = np.random.default_rng(R)
     for K, T, paths in ((8, 7, random_ids(rng, 8, 5, 80, 4)), (256, 5, random_ids(rng, 256, 3, 300, 256)),
                         (30, 6, [(c,) for c in range(30)] + random_ids(rng, 30, 4, 40, 3))):
-        narrow = _search_direct(cuda, "", 17 + K, R, K, T, 6, paths)
-        wide = _search_direct(cuda, "_wide", 17 + K, R, K, T, 6, paths)
-        assert len(narrow) == len(wide) and all(a == b for a, b in zip(narrow, wide)), (R, K)
+        run_both(cuda, np.random.default_rng(17 + K), R, K, T, 6, paths, quantum=0.5, direct=True)
 
 
 def test_wide_refuses_unsupported_shapes_before_launch(cuda):
@@ -123,13 +84,13 @@ def test_wide_refuses_unsupported_shapes_before_launch(cuda):
         len_pow = torch.ones(T + 1, dtype=torch.float64, device=cuda)
         pool = (full((1, R), torch.float64), full((1, R)), full((1, R)), full((1, R, T)), full((1, 4)))
         out = (full((1, R), torch.float32), full((1, R)), full((1, R)), full((1, R)), full((1, R, T)), full((R, p + 1)))
-        st = L.mevi_beam_step_var_wide_f32(
+        st = L.mevi_beam_step_var_f32(
             hip.ptr(logits), hip.ptr(scores), hip.ptr(node), hip.ptr(prefix), hip.ptr(anc), 1, R, K, p, T, hip.ptr(tree.mask[0]),
             hip.ptr(tree.base[0]), hip.ptr(tree.ends[0]), tree.base[0].numel(), hip.ptr(len_pow), *(hip.ptr(t) for t in pool),
             *(hip.ptr(t) for t in out), hip.stream_ptr())
         assert st != 0
         with pytest.raises(hip.MeviHipError, match=match):
-            hip.check(st, "mevi_beam_step_var_wide_f32")
+            hip.check(st, "mevi_beam_step_var_f32")
         torch.cuda.synchronize()
         assert all(bool((t == 77).all()) for t in pool + out)
         return pool, out, scores, prefix, len_pow
@@ -141,10 +102,10 @@ def test_wide_refuses_unsupported_shapes_before_launch(cuda):
     pool, out, scores, prefix, len_pow = attempt(129, 8, 0, 4, "R <= 128")
     fin = (torch.full((129, 4), 77, dtype=torch.int64, device=cuda), torch.full((129,), 77.0, dtype=torch.float64, device=cuda),
            torch.full((129,), 77, dtype=torch.int32, device=cuda))
-    st = L.mevi_beam_finalize_var_wide_f32(hip.ptr(scores), hip.ptr(prefix), 1, 129, 4, hip.ptr(len_pow), *(hip.ptr(t) for t in pool),
-                                           *(hip.ptr(t) for t in fin), hip.stream_ptr())
+    st = L.mevi_beam_finalize_var_f32(hip.ptr(scores), hip.ptr(prefix), 1, 129, 4, hip.ptr(len_pow), *(hip.ptr(t) for t in pool),
+                                      *(hip.ptr(t) for t in fin), hip.stream_ptr())
     with pytest.raises(hip.MeviHipError, match="R <= 128"):
-        hip.check(st, "mevi_beam_finalize_var_wide_f32")
+        hip.check(st, "mevi_beam_finalize_var_f32")
     torch.cuda.synchronize()
     assert all(bool((t == 77).all()) for t in fin + pool)
 

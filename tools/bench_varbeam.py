@@ -6,12 +6,12 @@ k30_c30-style tree (hierarchical k-means ids: lengths 4 .. 6) over 8.8 M ids, t5
   timeout 60 python tools/bench_varbeam.py --share-from DIR/<host>/varbeam_kernel_stats.csv     (no GPU: reads the stats file)
 
   timeout -k 10 500 python tools/bench_varbeam.py --beams 100 --depth 8 --ids 2000000 --queries 1024 --batch 128 --variable-only   (pure-NCI shape)
-  timeout -k 10 120 python tools/bench_varbeam.py --steps-only --depth 8     (the beam-step kernels alone: narrow 32, wide 32 / 64 / 100)
+  timeout -k 10 120 python tools/bench_varbeam.py --steps-only --depth 8     (the beam-step kernel alone, at --step-beams 1,4,10,32,64,100)
 
-Options: [--ids N] [--queries N] [--batch N] [--beams R] [--depth M] [--steps-only] [--variable-only] [--out file.json].  --beams > 32 runs the
-wide kernel pair (mevi_beam_step_var_wide_f32); --depth M = ids of at most M codes (lengths M - 2 .. M), M + 1 decoder
-positions (more than 8: the 9 .. 16-key cached attention).  Every GPU step runs under its own time limit, the steps
-chained with && so that nothing starts after one of them failed.
+Options: [--ids N] [--queries N] [--batch N] [--beams R] [--depth M] [--steps-only] [--step-beams R,R,...] [--variable-only]
+[--out file.json].  --depth M = ids of at most M codes (lengths M - 2 .. M), M + 1 decoder positions (more than 8: the
+9 .. 16-key cached attention).  Every GPU step runs under its own time limit, the steps chained with && so that nothing
+starts after one of them failed.
 
 Reports the host tree build (seconds), the variable-depth search (queries/s) and, measured in the same process on the same
 model, the fixed-depth search over the shared-sons tree (M = 6, K = 30) it is to be compared with; --share-from adds
@@ -37,9 +37,9 @@ def synthetic_ids(n, rng, M=6):
     return rng.integers(0, K, size=(n, M)), lengths
 
 
-def step_times(dev, M, nq, rng, reps=20):
-    """Per-launch time of the beam-step kernels alone at (nq queries, K = 30, T = M + 2, step p = 2 of a three-level tree,
-    random logits): the narrow kernel at 32 beams, the wide one at 32 (forced), 64 and 100."""
+def step_times(dev, M, nq, rng, beam_counts, reps=20):
+    """Per-launch time of mevi_beam_step_var_f32 alone at (nq queries, K = 30, T = M + 2, step p = 2 of a three-level tree,
+    random logits) for every beam count of `beam_counts`."""
     import torch
 
     from mevi_amd import hip, nci
@@ -48,9 +48,8 @@ def step_times(dev, M, nq, rng, reps=20):
     codes, lengths = synthetic_ids(200000, rng, M)
     tree = nci.RaggedPrefixTree(codes, K, dev, lengths=lengths, levels=M + 1)
     n_nodes = tree.base[p].numel()
-    out = {}
-    for name, fn, beams in (("narrow_R32", "mevi_beam_step_var_f32", 32), ("wide_R32", "mevi_beam_step_var_wide_f32", 32),
-                            ("wide_R64", "mevi_beam_step_var_wide_f32", 64), ("wide_R100", "mevi_beam_step_var_wide_f32", 100)):
+    out, fn = {}, "mevi_beam_step_var_f32"
+    for beams in beam_counts:
         i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)                   # noqa: E731
         logits = torch.randn((nq * beams, K + 1), device=dev) * 2
         scores = -torch.rand((nq, beams), device=dev).cumsum(1)
@@ -80,7 +79,7 @@ def step_times(dev, M, nq, rng, reps=20):
                 t.zero_()
         ev[1].record()
         torch.cuda.synchronize()
-        out[name + "_us"] = round((with_reset - ev[0].elapsed_time(ev[1])) / reps * 1e3, 1)
+        out[f"R{beams}_us"] = round((with_reset - ev[0].elapsed_time(ev[1])) / reps * 1e3, 1)
     return out
 
 
@@ -103,6 +102,7 @@ def main():
     ap.add_argument("--beams", type=int, default=10)
     ap.add_argument("--depth", type=int, default=6)
     ap.add_argument("--steps-only", action="store_true")
+    ap.add_argument("--step-beams", default="1,4,10,32,64,100", help="beam counts --steps-only times")
     ap.add_argument("--variable-only", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--share-from", default=None)
@@ -119,7 +119,8 @@ def main():
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(0)
     if a.steps_only:
-        out = {"shape": {"queries": a.batch, "K": K, "max_codes": M}, "beam_step": step_times(dev, M, a.batch, rng)}
+        out = {"shape": {"queries": a.batch, "K": K, "max_codes": M},
+               "beam_step": step_times(dev, M, a.batch, rng, [int(r) for r in a.step_beams.split(",")])}
         print(json.dumps(out))
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

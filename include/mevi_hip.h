@@ -136,6 +136,42 @@ int mevi_pack_lists_i64(const float *scores, const int64_t *ids, int64_t n, int6
 int mevi_topk_merge_packed_f32(const int64_t *packed, int64_t nlists, int64_t nq, int64_t k_in, int64_t k_out,
                                int truncated, float *out_score, int64_t *out_id, uint8_t *unproven, void *stream);
 
+/* IVF-Flat search: `index.search(query, k)` of the factory string "IVF<n>,Flat", the reference script's default
+ * (MEVI/faiss_search.py:13-21,89: faiss IndexIVFFlat.search with an inner-product quantiser), given the probe table.
+ *   q f32 [nq, dim]; docs f32 [nd, dim] LIST-MAJOR (the rows of list l are [list_offsets[l], list_offsets[l+1]));
+ *   list_offsets device i64 [nlist + 1], ascending from 0 to nd; row_ids device i64 [nd]: document id of a list-major
+ *   row, every id in [0, 2^32) and no id twice (NULL: the id is the row); max_list_len >= the longest list (host-known);
+ *   probe device i32 [nq, nprobe]: the lists a query scans -- an entry < 0 or >= nlist is an empty probe, a list named
+ *   twice in a row counts once.
+ *   out f32 / i64 [nq, k]: per query the exact top-k among the rows of its probed lists.  Scores are the sequential fmaf
+ *   chains over dim of mevi_ip_topk_f32 (k = 0..dim-1 from +0; same bits), order is score descending then id ascending,
+ *   padding -FLT_MAX / -1 when fewer than k rows are probed.  Selection runs over all probed rows of a query at once,
+ *   so nprobe * k is not limited by the merge's 16384.
+ *   The coarse quantiser is the same call: docs = the centroids as ONE list (list_offsets {0, nlist}), probe all zero,
+ *   k = nprobe, row_ids NULL -> out_id is the probe table (score descending, list ascending).
+ * Stream-ordered and graph-capturable: no host synchronisation, no device-to-host copy, no allocation, no environment
+ * variable; grids and the workspace follow from nq, nprobe, k, dim, nlist, max_list_len alone, what depends on the data
+ * (pairs per list, rows per query) stays on the device.  Queries are walked in tiles inside the call, so the workspace is
+ * capped: mevi_ivf_scan_workspace_bytes() <= MEVI_IVF_SCAN_WORKSPACE_CAP for every shape (candidate scores of a tile
+ * <= 2 GiB, everything else <= 160 MiB); 0 = shape outside the envelope.
+ *   Refused before any launch: dim % 4 != 0, k outside 1..4096, nprobe outside 1..256, nd > 2^31 - 1 (ids must fit 32
+ *   bits), nlist > 262144 or nprobe * max_list_len * 4 bytes > 2 GiB (MEVI_ERR_UNSUPPORTED); null pointers, q / docs not
+ *   16-byte, offsets / ids not 8-byte, workspace not 256-byte aligned, max_list_len > nd (MEVI_ERR_INVALID_ARG); a
+ *   workspace below mevi_ivf_scan_workspace_bytes (MEVI_ERR_WORKSPACE).
+ *   MEVI_IVF_SCAN_PAIR_TILE (query, slot) pairs of a list share one pass over MEVI_IVF_SCAN_ROW_BLOCK of its rows. */
+#define MEVI_IVF_SCAN_PAIR_TILE 64
+#define MEVI_IVF_SCAN_ROW_BLOCK 128
+#define MEVI_IVF_SCAN_WORKSPACE_CAP (((size_t)2 << 30) + ((size_t)160 << 20))
+size_t mevi_ivf_scan_workspace_bytes(int64_t nq, int64_t nprobe, int64_t k, int64_t dim, int64_t nlist,
+                                     int64_t max_list_len);
+/* Queries per tile of the call above (host arithmetic; 0 = outside the envelope): every tile of that many queries passes
+ * over the rows of the lists it probes once more, so ceil(nq / tile) is what a caller weighs against another search. */
+int64_t mevi_ivf_scan_query_tile(int64_t nq, int64_t nprobe, int64_t k, int64_t dim, int64_t nlist, int64_t max_list_len);
+int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const int64_t *list_offsets,
+                           const int64_t *row_ids, int64_t nd, int64_t nlist, int64_t max_list_len, int64_t dim,
+                           const int32_t *probe, int64_t nprobe, int64_t k, float *out_score, int64_t *out_id,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------
  * Residual-quantisation encode: codes[n, M] (int32, values in [0, K)).
  * Replaces pq.get_rq_document_cluster / the index path of forward_rq with

@@ -175,6 +175,54 @@ def topk_merge(scores, ids, k_out):
     return out_s, out_i
 
 
+IVF_PAIR_TILE = 64                  # MEVI_IVF_SCAN_PAIR_TILE: (query, slot) pairs of a list that share one pass over its rows
+IVF_ROW_BLOCK = 128                 # MEVI_IVF_SCAN_ROW_BLOCK: rows of a list per work item of the scan
+IVF_WORKSPACE_CAP = (2 << 30) + (160 << 20)     # MEVI_IVF_SCAN_WORKSPACE_CAP
+IVF_MAX_NPROBE = 256
+
+
+def ivf_scan_workspace_bytes(nq, nprobe, k, dim, nlist, max_list_len):
+    """Bytes of workspace `ivf_scan_topk` needs (host arithmetic; 0 = shape outside the kernel's envelope)."""
+    return int(hip.lib().mevi_ivf_scan_workspace_bytes(nq, nprobe, k, dim, nlist, max_list_len))
+
+
+def ivf_scan_query_tile(nq, nprobe, k, dim, nlist, max_list_len):
+    """Queries per tile of `ivf_scan_topk` (0 = outside the envelope): each tile scans the lists it probes once more."""
+    return int(hip.lib().mevi_ivf_scan_query_tile(nq, nprobe, k, dim, nlist, max_list_len))
+
+
+def ivf_scan_topk(query, docs, list_offsets, row_ids, max_list_len, probe, k, out=None, workspace=None):
+    """Exact top-k of every query among the rows of the lists its probe row names (mevi_ivf_scan_topk_f32).
+
+    query f32 [nq, dim]; docs f32 [nd, dim] list-major; list_offsets i64 [nlist + 1] on the device; row_ids i64 [nd] or None
+    (id = row); probe i32 [nq, nprobe] (entries outside [0, nlist) are empty, a repeated list counts once).
+    Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
+    `out` = (scores, ids) and `workspace` (uint8, ivf_scan_workspace_bytes) preallocated nothing is allocated either."""
+    hip.require_gpu()
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2 and docs.is_contiguous() and docs.shape[1] == query.shape[1]
+    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
+    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
+    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == docs.shape[0])
+    nq, dim = query.shape
+    nd, nlist, nprobe = docs.shape[0], list_offsets.numel() - 1, probe.shape[1]
+    L = hip.lib()
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
+    out_s, out_i = out
+    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    if nq == 0:
+        return out_s, out_i
+    if workspace is None:
+        workspace = torch.empty(L.mevi_ivf_scan_workspace_bytes(nq, nprobe, k, dim, nlist, max_list_len), dtype=torch.uint8, device=query.device)
+    with hip.device_guard(query.device):
+        st = L.mevi_ivf_scan_topk_f32(hip.ptr(query), nq, hip.ptr(docs), hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids),
+                                      nd, nlist, max_list_len, dim, hip.ptr(probe), nprobe, k, hip.ptr(out_s), hip.ptr(out_i),
+                                      hip.ptr(workspace) if workspace.numel() else None, workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_ivf_scan_topk_f32")
+    return out_s, out_i
+
+
 def shard_range(n_rows, rank, world_size):
     """Contiguous row shard [start, end) of rank: ceil(n/world) rows each."""
     per = (n_rows + world_size - 1) // world_size

@@ -11,6 +11,15 @@ against the oracle -- given the centroids:
   * search: the exact top-k (score desc, id asc, faiss padding) among the documents of the query's `nprobe` best lists.
 Because the result is approximate by construction, `search` also runs the exact search and reports recall against it
 (stderr, so the script's stdout stays the reference's).  `nprobe` comes from MEVI_IVF_NPROBE (faiss default: 1).
+
+`IVFFlatIndex.search` is two stream-ordered calls of one C-ABI entry point (mevi_ivf_scan_topk_f32, csrc/ivf_scan.hip):
+the coarse quantiser -- the centroids as one list every query probes, k = nprobe -- and the scan of the probed lists,
+which groups the (query, slot) pairs by list on the device, shares every pass over a list's rows among the pairs that
+probe it and selects each query's top-k over all its probed rows at once.  Nothing is copied to the host, so a search of
+up to GRAPH_MAX_QUERIES queries can be captured and replayed as one graph (`search_graph`).  `search_lists` is the
+earlier host loop (one exact search per probed list + a merge): same bits; it serves the shapes outside the scan's
+envelope, the regimes where it measured faster (scan_wanted: many query tiles over few long lists) and every shape when
+MEVI_IVF_SCAN=lists.
 """
 import os
 import re
@@ -23,6 +32,12 @@ from . import dense, ops, rq
 
 MAX_POINTS_PER_CENTROID = 256     # faiss ClusteringParameters defaults
 NITER = 25
+GRAPH_MAX_QUERIES = 32            # search_graph: the batch sizes of faiss_search.profile / latency_b1
+# where `search` takes the device scan (profiles/ivf_scan_c2.json, 8.8 M x 768, k = 1000): up to SCAN_MAX_TILES query tiles it
+# beat the host loop at IVF100 and IVF4096 alike (6980 queries at nprobe 1: 4 and 3 tiles); with more tiles it still did at
+# IVF4096 (11 and 42 tiles: 123 vs 544 ms, 436 vs 795 ms) and lost at IVF100 (15 and 60 tiles: 232 vs 129 ms, 999 vs 255 ms)
+SCAN_MAX_TILES = 4
+SCAN_ANY_TILES_NLIST = 4096
 
 
 def parse_factory(param):
@@ -74,9 +89,53 @@ class IVFFlatIndex:
         self.docs = docs[order].contiguous()
         self.offsets = torch.zeros(nlist + 1, dtype=torch.int64)
         self.offsets[1:] = torch.cumsum(torch.bincount(self.list_of.long(), minlength=nlist), 0).cpu()
+        self.offsets_dev = self.offsets.to(docs.device)
+        self.max_list_len = int((self.offsets[1:] - self.offsets[:-1]).max()) if nlist else 0
+        self.centroid_offsets = torch.tensor([0, nlist], dtype=torch.int64, device=docs.device)   # the quantiser's one list
+
+    def scan_wanted(self, nq, k, nprobe):
+        """True when `search` takes the device scan: the shape is inside its envelope (a workspace size exists for both of its
+        calls), MEVI_IVF_SCAN does not ask for the host loop, and the regime is one where the scan measured at least as fast
+        (DESIGN 4.1f): the scan passes over the probed lists once per query tile, the host loop once per probed list, so many
+        tiles over few lists -- thousands of queries at nprobe >= 4 on an index of a hundred long lists -- stay with the loop."""
+        if os.environ.get("MEVI_IVF_SCAN", "scan") == "lists" or nq < 1 or nprobe > dense.IVF_MAX_NPROBE:
+            return False
+        dim = self.docs.shape[1]
+        tile = dense.ivf_scan_query_tile(nq, nprobe, k, dim, self.nlist, self.max_list_len)
+        if tile < 1 or dense.ivf_scan_workspace_bytes(nq, 1, nprobe, dim, 1, self.nlist) < 1:
+            return False
+        return -(-nq // tile) <= SCAN_MAX_TILES or self.nlist >= SCAN_ANY_TILES_NLIST
 
     def search(self, query, k, nprobe=1):
         """(scores f32 [nq, k] desc, ids i64 [nq, k]; -FLT_MAX / -1 padding when the probed lists hold fewer than k)."""
+        nprobe = max(1, min(int(nprobe), self.nlist))
+        if not self.scan_wanted(query.shape[0], k, nprobe):
+            return self.search_lists(query, k, nprobe)
+        return self.search_scan(query.contiguous(), k, nprobe)
+
+    def search_scan(self, query, k, nprobe, buffers=None):
+        """The two device calls.  `buffers` (search_graph) = preallocated (zero probe, coarse out, i32 probe, out, two workspaces)."""
+        nq = query.shape[0]
+        dev = query.device
+        if buffers is None:
+            zero = torch.zeros((nq, 1), dtype=torch.int32, device=dev)
+            coarse = dense.ivf_scan_topk(query, self.centroids, self.centroid_offsets, None, self.nlist, zero, nprobe)
+            probe = coarse[1].to(torch.int32)                              # [nq, nprobe] best lists (score desc, list asc)
+            return dense.ivf_scan_topk(query, self.docs, self.offsets_dev, self.ids, self.max_list_len, probe, k)
+        zero, coarse, probe, out, ws_coarse, ws_scan = buffers
+        dense.ivf_scan_topk(query, self.centroids, self.centroid_offsets, None, self.nlist, zero, nprobe, out=coarse, workspace=ws_coarse)
+        probe.copy_(coarse[1])
+        return dense.ivf_scan_topk(query, self.docs, self.offsets_dev, self.ids, self.max_list_len, probe, k, out=out, workspace=ws_scan)
+
+    def search_graph(self, nq, k, nprobe=1):
+        """A captured graph of `search` for exactly nq <= GRAPH_MAX_QUERIES queries: `.run(query)` -> (scores, ids)."""
+        nprobe = max(1, min(int(nprobe), self.nlist))
+        if not 1 <= nq <= GRAPH_MAX_QUERIES or not self.scan_wanted(nq, k, nprobe):
+            raise ValueError(f"search_graph: nq={nq} k={k} nprobe={nprobe} is outside the device scan (1..{GRAPH_MAX_QUERIES} queries)")
+        return SearchGraph(self, nq, k, nprobe)
+
+    def search_lists(self, query, k, nprobe=1):
+        """`search` as a host loop over the probed lists: one exact search per list, then a merge.  Same result, bit for bit."""
         nq = query.shape[0]
         nprobe = max(1, min(int(nprobe), self.nlist))
         dev = query.device
@@ -101,6 +160,36 @@ class IVFFlatIndex:
             # inside one list the local order is (score desc, LOCAL row asc) = (score desc, id asc): ids ascend in a list
             return out_s, out_i
         return dense.topk_merge(cand_s, cand_i, k)
+
+
+class SearchGraph:
+    """`IVFFlatIndex.search` of a fixed (nq, k, nprobe) as one replayed graph: static query, probe and output buffers and both
+    workspaces are allocated here, the first search runs eagerly (it loads the kernels), the second is captured."""
+
+    def __init__(self, index, nq, k, nprobe):
+        dev, dim = index.docs.device, index.docs.shape[1]
+        self.query = torch.zeros((nq, dim), dtype=torch.float32, device=dev)
+
+        def empty(n, dtype):
+            return torch.empty((nq, n), dtype=dtype, device=dev)
+
+        def ws(*shape):
+            return torch.empty(dense.ivf_scan_workspace_bytes(*shape), dtype=torch.uint8, device=dev)
+
+        buffers = (torch.zeros((nq, 1), dtype=torch.int32, device=dev), (empty(nprobe, torch.float32), empty(nprobe, torch.int64)),
+                   empty(nprobe, torch.int32), (empty(k, torch.float32), empty(k, torch.int64)),
+                   ws(nq, 1, nprobe, dim, 1, index.nlist), ws(nq, nprobe, k, dim, index.nlist, index.max_list_len))
+        index.search_scan(self.query, k, nprobe, buffers)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = index.search_scan(self.query, k, nprobe, buffers)
+        self.index, self.buffers = index, buffers          # the graph holds their addresses
+
+    def run(self, query):
+        self.query.copy_(query)
+        self.graph.replay()
+        return self.out[0].clone(), self.out[1].clone()
 
 
 def recall_report(approx_ids, exact_ids, cutoffs=(1, 10, 100, 1000)):

@@ -145,8 +145,8 @@ int mevi_topk_merge_packed_f32(const int64_t *packed, int64_t nlists, int64_t nq
  *   twice in a row counts once.
  *   out f32 / i64 [nq, k]: per query the exact top-k among the rows of its probed lists.  Scores are the sequential fmaf
  *   chains over dim of mevi_ip_topk_f32 (k = 0..dim-1 from +0; same bits), order is score descending then id ascending,
- *   padding -FLT_MAX / -1 when fewer than k rows are probed.  Selection runs over all probed rows of a query at once,
- *   so nprobe * k is not limited by the merge's 16384.
+ *   padding -FLT_MAX / -1 when fewer than k rows are probed.  NaN/inf scores: order unspecified.  Selection runs over
+ *   all probed rows of a query at once, so nprobe * k is not limited by the merge's 16384.
  *   The coarse quantiser is the same call: docs = the centroids as ONE list (list_offsets {0, nlist}), probe all zero,
  *   k = nprobe, row_ids NULL -> out_id is the probe table (score descending, list ascending).
  * Stream-ordered and graph-capturable: no host synchronisation, no device-to-host copy, no allocation, no environment

@@ -172,6 +172,43 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
                            const int32_t *probe, int64_t nprobe, int64_t k, float *out_score, int64_t *out_id,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* Fine stage: the best k documents of a query's beam clusters (the running top-k of --knn_topk_by_step,
+ * MEVI/main_models.py:3915-4014, 3919-3995), from beam keys to a fixed-shape top-k in one call.
+ *   q f32, row stride ldq: [nq] rows (per_beam = 0) or [nq * R] rows (per_beam = 1: row b * R + j scores the candidates of
+ *   beam j of query b, the pairing of --query_encoder nci); emb f32 [n_docs, dim] contiguous;
+ *   cluster_keys i64 [n_clusters] ascending and distinct, cluster_offsets i64 [n_clusters + 1], cluster_docs i64: the CSR
+ *   arrays of the cluster index (key(code) = sum_j code[j] * K^(M-1-j)); beam_keys i64 [nq, R].  All device pointers.
+ *   Per query b the walk j = 0..R-1 appends the documents of the cluster whose key is beam_keys[b, j], in stored order; a
+ *   key that is negative or not among cluster_keys appends nothing, a key that occurs twice in the row is listed and scored
+ *   again.  A document id outside [0, n_docs) is skipped: it is neither scored nor counted (it still takes its place in
+ *   the walk where max_cand is concerned).  Scores are the sequential f32 fmaf chains over dim from +0 of
+ *   mevi_pair_dot_f32 (same bits).
+ *   out_score f32 / out_id i64 [nq, k]: the first k candidates in (score descending, id ascending) order, padding
+ *   -FLT_MAX / -1; out_ndoc i32 [nq]: the candidates of the whole walk, repeats included (saturating at 2^31 - 1).  NaN
+ *   scores: order unspecified.
+ *   max_cand (host-known, >= 1) bounds the entries of one query's walk: grids, LDS and the workspace follow from
+ *   nq, R, k, dim and max_cand alone.  Of a longer walk only the first max_cand entries in walk order compete, out_ndoc
+ *   still reports the whole walk, and nothing is written outside the outputs and the workspace.
+ * Stream-ordered and graph-capturable: no host synchronisation, no device-to-host copy, no allocation, no environment
+ * variable, three launches per query tile (four with max_cand > 2048) whatever the data.  Queries are walked in tiles inside the call, so
+ * mevi_fine_topk_workspace_bytes() <= MEVI_FINE_TOPK_WORKSPACE_CAP for every shape (scores and ids of a tile <= 1 GiB,
+ * everything else <= 16 MiB); 0 = shape outside the envelope.
+ *   Refused before any launch, also with nq == 0: dim % 4 != 0, k outside 1..4096, R outside 1..128, n_docs > 2^31 - 1,
+ *   max_cand * 8 bytes > 1 GiB (MEVI_ERR_UNSUPPORTED); max_cand < 1, ldq < dim or ldq % 4 != 0 (MEVI_ERR_INVALID_ARG).
+ *   nq == 0 then returns MEVI_OK without a launch.  With nq > 0: null pointers (the three CSR arrays may be null when
+ *   n_clusters == 0), q / emb not 16-byte, the i64 arrays not 8-byte, the workspace not 256-byte aligned
+ *   (MEVI_ERR_INVALID_ARG); a workspace below mevi_fine_topk_workspace_bytes (MEVI_ERR_WORKSPACE). */
+#define MEVI_FINE_TOPK_WORKSPACE_CAP (((size_t)1 << 30) + ((size_t)16 << 20))
+size_t mevi_fine_topk_workspace_bytes(int64_t nq, int64_t R, int64_t k, int64_t dim, int64_t max_cand);
+/* Queries per tile of the call below (host arithmetic; 0 = outside the envelope). */
+int64_t mevi_fine_topk_query_tile(int64_t nq, int64_t R, int64_t k, int64_t dim, int64_t max_cand);
+int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, int64_t R,
+                       const float *emb, int64_t n_docs, int64_t dim,
+                       const int64_t *cluster_keys, const int64_t *cluster_offsets, const int64_t *cluster_docs,
+                       int64_t n_clusters, const int64_t *beam_keys, int64_t max_cand, int64_t k,
+                       float *out_score, int64_t *out_id, int32_t *out_ndoc,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------
  * Residual-quantisation encode: codes[n, M] (int32, values in [0, K)).
  * Replaces pq.get_rq_document_cluster / the index path of forward_rq with

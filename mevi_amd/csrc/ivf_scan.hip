@@ -36,6 +36,7 @@
 
 #include "common.h"
 #include "mfma_pp.h"
+#include "select_topk.h"
 
 namespace mevi {
 namespace {
@@ -49,7 +50,6 @@ constexpr int IVF_MAX_NPROBE = 256;
 constexpr int64_t IVF_MAX_NLIST = 262144;
 constexpr int64_t IVF_MAX_QT = 4096;                      // queries per tile: 64 bitmap words per list
 constexpr size_t IVF_CAND_CAP = (size_t)2 << 30;
-static_assert(SEL_THREADS == 1024, "ivf_select_kernel reduces over 16 waves");
 static_assert(IVF_PAIR_TILE == 64 && IVF_ROW_BLOCK == 128, "the scan kernel's wave layout is 4 x (32 rows x 64 pairs)");
 
 struct IvfPlan {
@@ -269,65 +269,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) ivf_scan_kernel(const float *__r
 }
 
 // ---- selection --------------------------------------------------------------------------------------------------------
-// hist[0, nb) holds at least `want` entries: the bin of the want-th entry counted from the TOP bin down, the entries above that
-// bin and the bin's own count -> bcast[0..2] (all threads, after the barrier).  nb is a multiple of 64.
-__device__ inline void top_bin(const int *hist, int nb, int want, int *bcast) {
-  const int t = threadIdx.x;
-  if (t < 64) {                                         // wave 0: lane 0 owns the highest bins
-    const int per = nb >> 6, top = nb - 1 - t * per;
-    int sum = 0;
-    for (int j = 0; j < per; ++j) sum += hist[top - j];
-    int incl = sum;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d);
-      if (t >= d) incl += o;
-    }
-    const int excl = incl - sum;
-    if (excl < want && incl >= want) {
-      int c = excl;
-      for (int j = 0; j < per; ++j) {
-        const int h = hist[top - j];
-        if (c + h >= want) {
-          bcast[0] = top - j;
-          bcast[1] = c;
-          bcast[2] = h;
-          break;
-        }
-        c += h;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// The want-th largest of key(score, row) over the candidates that pass `pred` (at least `want` of them), by three histogram
-// passes.  Returns the value; `need` = how many candidates EQUAL to it belong to the top `want`, `n_eq` = how many there are.
-template <typename Each, typename Key, typename Pred>
-__device__ uint32_t radix_select(Each each, Key key, Pred pred, int want, int *hist, int *bcast, int &need, int &n_eq) {
-  const int t = threadIdx.x;
-  uint32_t prefix = 0, mask = 0;
-  const int shifts[3] = {21, 10, 0}, bitsn[3] = {11, 11, 10};
-  for (int pass = 0; pass < 3; ++pass) {
-    const int shift = shifts[pass], nb = 1 << bitsn[pass];
-    for (int i = t; i < nb; i += SEL_THREADS) hist[i] = 0;
-    __syncthreads();
-    each([&](float s, uint32_t row) {
-      if (!pred(s, row)) return;
-      const uint32_t v = key(s, row);
-      if ((v & mask) == prefix) atomicAdd(&hist[(v >> shift) & (nb - 1)], 1);
-    });
-    __syncthreads();
-    top_bin(hist, nb, want, bcast);
-    prefix |= (uint32_t)bcast[0] << shift;
-    mask |= (uint32_t)(nb - 1) << shift;
-    want -= bcast[1];
-    n_eq = bcast[2];
-    __syncthreads();
-  }
-  need = want;
-  return prefix;
-}
-
+// The selection itself (histogram, radix select, id pass at the cut, final sort) is select_topk.h.
 __global__ void __launch_bounds__(SEL_THREADS) ivf_select_kernel(const float *__restrict__ cand, long long ld,
                                                                  const int32_t *__restrict__ clean,
                                                                  const int64_t *__restrict__ off,
@@ -335,9 +277,6 @@ __global__ void __launch_bounds__(SEL_THREADS) ivf_select_kernel(const float *__
                                                                  int max_len, float *__restrict__ out_s, int64_t *__restrict__ out_i) {
   __shared__ unsigned long long keys[IVF_MAX_K];
   __shared__ int hist[2048];
-  __shared__ int bcast[4];
-  __shared__ float range[32];
-  __shared__ int n_keys;
   const int q = blockIdx.x, t = threadIdx.x;
   const int32_t *slots = clean + (size_t)q * nprobe;
   const float *base = cand + (size_t)q * nprobe * (size_t)ld;
@@ -366,68 +305,7 @@ __global__ void __launch_bounds__(SEL_THREADS) ivf_select_kernel(const float *__
     const int l = slots[s];
     if (l >= 0) total += max(0ll, min((long long)max_len, off[l + 1] - off[l]));
   }
-  int P = 2;
-  while (P < k) P <<= 1;
-  for (int i = t; i < P; i += SEL_THREADS) keys[i] = 0ull;
-  if (t == 0) n_keys = 0;
-  __syncthreads();
-
-  uint32_t ts = 0, tid = 0;          // thresholds: score (order-preserving map), ~id inside the score's run of equals
-  bool cut = false;                  // the k-th place falls inside a run of equal scores
-  if (total > k) {
-    // Narrow first with bins that are LINEAR in the score between the query's lowest and highest: scores crowd a few
-    // exponents, so the radix passes' bins (sign, exponent, two mantissa bits at first) would take most candidates in a
-    // handful of LDS words, one atomic after the other.  The bin is a monotone function of the score (a rounded subtract, a
-    // rounded multiply by inv >= 0, a truncation, a clamp), so the k-th score lies in the bin top_bin finds and the radix
-    // passes only count that bin's candidates.
-    float lo = FLT_MAX, hi = -FLT_MAX;
-    each([&](float s, uint32_t) {
-      lo = fminf(lo, s);
-      hi = fmaxf(hi, s);
-    });
-    for (int d = 32; d > 0; d >>= 1) {
-      lo = fminf(lo, __shfl_xor(lo, d));
-      hi = fmaxf(hi, __shfl_xor(hi, d));
-    }
-    if ((t & 63) == 0) {
-      range[t >> 6] = lo;
-      range[16 + (t >> 6)] = hi;
-    }
-    for (int i = t; i < 2048; i += SEL_THREADS) hist[i] = 0;
-    __syncthreads();
-    for (int w = 0; w < SEL_THREADS / 64; ++w) {
-      lo = fminf(lo, range[w]);
-      hi = fmaxf(hi, range[16 + w]);
-    }
-    const float width = hi - lo;
-    const float inv = (width > 0.f && width < FLT_MAX) ? 2047.f / width : 0.f;
-    auto lbin = [lo, inv](float s) { return min(max((int)((s - lo) * inv), 0), 2047); };
-    each([&](float s, uint32_t) { atomicAdd(&hist[lbin(s)], 1); });
-    __syncthreads();
-    top_bin(hist, 2048, k, bcast);
-    const int bin = bcast[0], above = bcast[1];
-    __syncthreads();
-    int need, n_eq;
-    ts = radix_select(each, [](float s, uint32_t) { return f32_to_ord(s); }, [=](float s, uint32_t) { return lbin(s) == bin; },
-                      k - above, hist, bcast, need, n_eq);
-    if (n_eq > need) {
-      cut = true;
-      int need2, n_eq2;
-      tid = radix_select(each, [&](float, uint32_t row) { return ~id_of(row); },
-                         [ts](float s, uint32_t) { return f32_to_ord(s) == ts; }, need, hist, bcast, need2, n_eq2);
-    }
-  }
-  each([&](float s, uint32_t row) {
-    const uint32_t o = f32_to_ord(s);
-    if (o < ts) return;
-    const uint32_t id = id_of(row);
-    if (o > ts || !cut || ~id >= tid) {
-      const int at = atomicAdd(&n_keys, 1);
-      if (at < P) keys[at] = make_key(s, id);
-    }
-  });
-  __syncthreads();
-  bitonic_sort_desc<SEL_THREADS>(keys, P, t);
+  select_topk<SEL_THREADS>(each, id_of, total, k, keys, hist);
   for (int i = t; i < k; i += SEL_THREADS) {
     const unsigned long long key = keys[i];
     out_s[(size_t)q * k + i] = key ? key_score(key) : -FLT_MAX;

@@ -11,11 +11,10 @@
 //                 Bound: HBM on the gathered 3 KB rows (random rows; algorithmic bytes 4*dim per pair).
 //   segment_sort  per query: candidates -> (score desc, id asc) with the LDS bitonic sort on 64-bit keys.
 #include "common.h"
+#include "pair_dot.h"
 
 namespace mevi {
 namespace {
-
-constexpr int PD_LD = 36;  // floats per staged row (16-byte aligned, conflict-free b128 reads)
 
 __global__ __launch_bounds__(256) void pair_dot_kernel(const float *__restrict__ A, long long lda,
                                                       const long long *__restrict__ ia,
@@ -43,28 +42,9 @@ __global__ __launch_bounds__(256) void pair_dot_kernel(const float *__restrict__
     const int kk = s * 32;
     const bool in = kk + skq < dim;  // dim % 4 == 0
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
-      if (in) {
-        va = *reinterpret_cast<const float4 *>(ap[i] + kk);
-        vb = *reinterpret_cast<const float4 *>(bp[i] + kk);
-      }
-      *reinterpret_cast<float4 *>(&sa[wave][(srow + 8 * i) * PD_LD + skq]) = va;
-      *reinterpret_cast<float4 *>(&sb[wave][(srow + 8 * i) * PD_LD + skq]) = vb;
-    }
+    pd_stage_slab(sa[wave], sb[wave], ap, bp, kk, in, srow, skq);
     __syncthreads();
-    const float *ra = &sa[wave][lane * PD_LD];
-    const float *rb = &sb[wave][lane * PD_LD];
-#pragma unroll
-    for (int k4 = 0; k4 < 32; k4 += 4) {
-      const float4 x = *reinterpret_cast<const float4 *>(ra + k4);
-      const float4 y = *reinterpret_cast<const float4 *>(rb + k4);
-      acc = fmaf(x.x, y.x, acc);
-      acc = fmaf(x.y, y.y, acc);
-      acc = fmaf(x.z, y.z, acc);
-      acc = fmaf(x.w, y.w, acc);
-    }
+    acc = pd_chain_slab(&sa[wave][lane * PD_LD], &sb[wave][lane * PD_LD], acc);
   }
   const long long p = base + lane;
   if (p < n) out[p] = acc + 0.0f;

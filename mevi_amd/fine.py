@@ -10,6 +10,10 @@ The reference walks Python dicts and a CPU memmap per cluster with one H2D copy 
 <= 1024 rows; here the cluster -> doc list is a CSR index, all (query, doc) pairs of a batch are
 scored by ONE pair_dot launch on the HBM-resident embedding matrix and ordered by ONE segmented
 sort.  Order: score descending, ties by ascending doc id (torch.sort leaves ties unspecified).
+
+`FineStage.topk` / `topk_graph` are the same stage as ONE stream-ordered device call (mevi_fine_topk_f32, csrc/fine_topk.hip):
+beam keys on the device -> per query the best k documents and ndoc, nothing copied to the host.  New surface: `rerank` and its
+callers are untouched, and nothing is routed through it by default.
 """
 import numpy as np
 import torch
@@ -18,6 +22,7 @@ from . import ops
 from .rq import ClusterIndex
 
 MAX_SEGMENT = 16384
+TOPK_GRAPH_MAX_QUERIES = 32       # topk_graph: the batch sizes of latency_b1
 
 
 def f32_repr(values):
@@ -164,6 +169,56 @@ class FineStage:
         out = [(i_sorted[a:b], s_sorted[a:b]) for a, b in zip(seg[:-1], seg[1:])]
         return out, ndoc
 
+    # ---- beam clusters -> top-k on the device (csrc/fine_topk.hip) -------------------------------------------------------
+    def _device_index(self):
+        """The CSR arrays on the device, uploaded once (None x 3 for an index without clusters)."""
+        if self._dev_index is None:
+            self._dev_index = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)
+                                    for a in (self.index.keys, self.index.offsets, self.index.doc_ids))
+        return self._dev_index if len(self.index.keys) else (None, None, None)
+
+    def max_candidates(self, R):
+        """Host-known bound on one query's candidates: the R largest clusters together (computed once per index and R).  It
+        holds for beam rows of distinct clusters, which is what a beam search returns; a row that repeats a key can exceed it,
+        and then its walk is cut at the bound while ndoc still reports the whole walk."""
+        if not hasattr(self, "_max_cand"):
+            self._max_cand, self._sizes_desc = {}, np.sort(np.diff(np.asarray(self.index.offsets, dtype=np.int64)))[::-1]
+        if R not in self._max_cand:
+            self._max_cand[R] = max(1, int(self._sizes_desc[:R].sum()))
+        return self._max_cand[R]
+
+    def beam_keys(self, beam):
+        """beam codes [B, R, M] (i32 / i64) or keys i64 [B, R] on the device -> keys i64 [B, R]: ClusterIndex.code_keys'
+        formula, evaluated on the device."""
+        assert torch.is_tensor(beam) and beam.is_cuda, "topk takes the beam as a device tensor (rerank takes host arrays)"
+        if beam.dim() == 2:
+            assert beam.dtype == torch.int64
+            return beam.contiguous()
+        assert beam.dim() == 3 and beam.dtype in (torch.int32, torch.int64)
+        M = beam.shape[2]
+        if not hasattr(self, "_key_weights") or self._key_weights.numel() != M:
+            self._key_weights = torch.tensor([self.index.K ** (M - 1 - j) for j in range(M)], dtype=torch.int64, device=self.dev)
+        return (beam.to(torch.int64) * self._key_weights).sum(-1)
+
+    def topk(self, query_emb, beam, k, out=None, workspace=None, max_cand=None):
+        """The best k documents of every query's beam clusters, without a host copy: (scores f32 [B, k], ids i64 [B, k],
+        ndoc i32 [B]) on the device; the first k entries of `rerank`'s lists, bit for bit, padded with -FLT_MAX / -1, and its
+        ndoc.  query_emb f32 [B, dim], or [B * R, dim] for per-beam embeddings (as `rerank` infers it); `beam`: codes
+        [B, R, M] or keys i64 [B, R] on the device.  One mevi_fine_topk_f32 call on the current stream.  `max_cand`: the bound on
+        one query's candidates when `max_candidates(R)` is not one (rows that repeat a key)."""
+        keys = self.beam_keys(beam)
+        bound = self.max_candidates(keys.shape[1]) if max_cand is None else int(max_cand)
+        return ops.fine_topk(query_emb, self.emb, *self._device_index(), keys, bound, k, out=out, workspace=workspace)
+
+    def topk_graph(self, B, R, k, per_beam=False):
+        """A captured graph of `topk` for exactly B <= TOPK_GRAPH_MAX_QUERIES queries of R beams:
+        `.run(query_emb, beam_keys)` -> (scores, ids, ndoc)."""
+        if not 1 <= B <= TOPK_GRAPH_MAX_QUERIES:
+            raise ValueError(f"topk_graph: B={B} outside 1..{TOPK_GRAPH_MAX_QUERIES}")
+        if ops.fine_topk_workspace_bytes(B, R, k, self.emb.shape[1], self.max_candidates(R)) < 1:
+            raise ValueError(f"topk_graph: B={B} R={R} k={k} is outside the envelope of mevi_fine_topk_f32")
+        return TopkGraph(self, B, R, k, per_beam)
+
     def gt_scores(self, query_emb, gt_doc_ids):
         """q . emb[gt] for the hard-negative log line (main_models.py:4024-4045): list of f32 arrays."""
         lens = [len(g) for g in gt_doc_ids]
@@ -173,6 +228,31 @@ class FineStage:
         ia = torch.from_numpy(np.repeat(np.arange(len(lens), dtype=np.int64), lens)).to(self.dev)
         sc = ops.pair_dot(query_emb, ia, self.emb, ib).cpu().numpy()
         return np.split(sc, np.cumsum(lens)[:-1])
+
+
+class TopkGraph:
+    """`FineStage.topk` of a fixed (B, R, k, per_beam) as one replayed graph: static query, key and output buffers and the
+    workspace are allocated here, the first call runs eagerly (it loads the kernels), the second is captured."""
+
+    def __init__(self, stage, B, R, k, per_beam):
+        dev, dim = stage.dev, stage.emb.shape[1]
+        self.query = torch.zeros((B * R if per_beam else B, dim), dtype=torch.float32, device=dev)
+        self.keys = torch.full((B, R), -1, dtype=torch.int64, device=dev)
+        out = (torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int64, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev))
+        ws = torch.empty(ops.fine_topk_workspace_bytes(B, R, k, dim, stage.max_candidates(R)), dtype=torch.uint8, device=dev)
+        stage.topk(self.query, self.keys, k, out=out, workspace=ws)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = stage.topk(self.query, self.keys, k, out=out, workspace=ws)
+        self.stage, self.workspace = stage, ws             # the graph holds their addresses
+
+    def run(self, query_emb, beam_keys):
+        self.query.copy_(query_emb)
+        self.keys.copy_(beam_keys)
+        self.graph.replay()
+        return tuple(o.clone() for o in self.out)
 
 
 def coarse_ranks(beam_codes, gt_codes):

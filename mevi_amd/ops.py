@@ -815,6 +815,66 @@ def segment_aggregate_sort(scores, ids, seg_offsets, max_seg_len, mode):
     return out_s, out_i, counts
 
 
+FINE_TOPK_WORKSPACE_CAP = (1 << 30) + (16 << 20)      # MEVI_FINE_TOPK_WORKSPACE_CAP
+FINE_TOPK_SORT_MAX = 16384                            # candidates of one query the LDS sort of mevi_fine_topk_f32 holds
+
+
+def fine_topk_workspace_bytes(nq, R, k, dim, max_cand):
+    """Bytes of workspace `fine_topk` needs (host arithmetic; 0 = shape outside the kernel's envelope)."""
+    return int(hip.lib().mevi_fine_topk_workspace_bytes(nq, R, k, dim, max_cand))
+
+
+def fine_topk_query_tile(nq, R, k, dim, max_cand):
+    """Queries per tile of `fine_topk` (0 = outside the envelope)."""
+    return int(hip.lib().mevi_fine_topk_query_tile(nq, R, k, dim, max_cand))
+
+
+@hip.on_device
+def fine_topk(query, emb, cluster_keys, cluster_offsets, cluster_docs, beam_keys, max_cand, k, out=None, workspace=None):
+    """The best k documents of every query's beam clusters (mevi_fine_topk_f32).
+
+    query f32 [B, dim] or [B * R, dim] (row b * R + j scores beam j of query b), last dim contiguous; emb f32 [N, dim];
+    cluster_keys / cluster_offsets / cluster_docs i64 on the device: the CSR arrays of rq.ClusterIndex (all None: no cluster);
+    beam_keys i64 [B, R]; max_cand: host-known bound on one query's candidates.
+    Returns (scores f32 [B, k] desc, ids i64 [B, k], ndoc i32 [B]; ties by ascending id; -FLT_MAX / -1 padding).
+    Stream-ordered: with `out` = (scores, ids, ndoc) and `workspace` (uint8, fine_topk_workspace_bytes) preallocated nothing
+    is allocated either."""
+    hip.require_gpu()
+    query, rows, dim, ldq = _rows2d(_f32(query))
+    if rows == 1:
+        ldq = dim                                      # a single row's stride is arbitrary (numpy hands over 0)
+    emb = _f32(emb)
+    assert emb.dim() == 2 and emb.is_contiguous() and emb.shape[1] == dim
+    assert beam_keys.is_cuda and beam_keys.dtype == torch.int64 and beam_keys.dim() == 2 and beam_keys.is_contiguous()
+    B, R = beam_keys.shape
+    assert rows in (B, B * R), (rows, B, R)
+    per_beam = 1 if rows != B else 0
+    csr = (cluster_keys, cluster_offsets, cluster_docs)
+    if cluster_keys is None:
+        assert cluster_offsets is None and cluster_docs is None
+        n_clusters = 0
+    else:
+        assert all(a.is_cuda and a.dtype == torch.int64 and a.is_contiguous() for a in csr)
+        n_clusters = cluster_keys.numel()
+        assert cluster_offsets.numel() == n_clusters + 1
+    dev = query.device
+    if out is None:
+        out = (torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int64, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    out_s, out_i, out_n = out
+    assert out_s.shape == (B, k) and out_i.shape == (B, k) and out_n.shape == (B,)
+    assert out_s.is_contiguous() and out_i.is_contiguous() and out_n.is_contiguous()
+    L = hip.lib()
+    if workspace is None:
+        workspace = torch.empty(L.mevi_fine_topk_workspace_bytes(B, R, k, dim, max_cand), dtype=torch.uint8, device=dev)
+    st = L.mevi_fine_topk_f32(hip.ptr(query), ldq, per_beam, B, R, hip.ptr(emb), emb.shape[0], dim,
+                              *(None if a is None else hip.ptr(a) for a in csr), n_clusters, hip.ptr(beam_keys), int(max_cand), k,
+                              hip.ptr(out_s), hip.ptr(out_i), hip.ptr(out_n), hip.ptr(workspace) if workspace.numel() else None,
+                              workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_fine_topk_f32")
+    return out_s, out_i, out_n
+
+
 QPOOL_PIECES = {"enc": 1, "encmask": 2, "dec": 4, "emb": 8}
 QPOOL_ACCUM = {"maxpool": 0, "avgpool": 16, "attenpool": 32}
 

@@ -172,6 +172,57 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
                            const int32_t *probe, int64_t nprobe, int64_t k, float *out_score, int64_t *out_id,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* IVF-Flat build, step 1: `index.train` / `index.add` label every row with its best centroid (faiss IndexIVFFlat with an
+ * IndexFlatIP quantiser, MEVI/faiss_search.py:17-19) -- the nearest centroid by inner product, without the [n, nlist]
+ * score matrix.
+ *   x f32 [n, dim], centroids f32 [nlist, dim], both row-major and contiguous;
+ *   list_of i32 [n]: the LOWEST c that attains max_c chain(x_r, centroid_c); best_score f32 [n] (may be NULL): that maximum.
+ *   chain = the sequential fmaf chain from +0 over k = 0..dim-1: the bits of mevi_ip_topk_f32 with k = 1, of
+ *   mevi_gemm_nt_f32 and of the scan above.  NaN / +-inf scores are outside the contract (the label then is some value in
+ *   [0, nlist)).
+ *   A workgroup keeps MEVI_IVF_ASSIGN_ROWS rows and walks the centroids in tiles of MEVI_IVF_ASSIGN_COLS with a running
+ *   (best score, lowest index) in registers; with fewer than MEVI_IVF_ASSIGN_SPLIT_WGS row blocks the walk is split among
+ *   workgroups (in tiles of half that width while row blocks x tiles stay below that number) and the parts are combined
+ *   from the workspace.  No atomics: the result does not depend on scheduling.
+ * Stream-ordered and graph-capturable: no host synchronisation, no copy, no allocation, no environment variable.
+ *   Envelope: dim % 4 == 0 (dim < 2^24), 1 <= nlist <= MEVI_IVF_BUILD_MAX_NLIST, 0 <= n < 2^31; n == 0 returns MEVI_OK
+ *   without a launch.  mevi_ivf_assign_workspace_bytes: pure host arithmetic, positive inside the envelope, never smaller
+ *   for a larger argument, 0 outside.
+ *   Refused before any launch, naming the argument: n or dim negative (MEVI_ERR_INVALID_ARG); dim % 4 != 0, nlist outside
+ *   1..262144, n >= 2^31 (MEVI_ERR_UNSUPPORTED); with n > 0: x, centroids, list_of or workspace null, x / centroids not
+ *   16-byte, list_of / best_score not 4-byte, workspace not 256-byte aligned (MEVI_ERR_INVALID_ARG); a workspace below
+ *   mevi_ivf_assign_workspace_bytes (MEVI_ERR_WORKSPACE; the message carries the needed size).
+ * k-means on the C ABI (what mevi_amd/ivf.py: train_centroids does): per iteration mevi_ivf_assign_f32(sample, centroids)
+ * -> labels, then mevi_cluster_means_f32(sample, labels) -> the new centroids and the list sizes. */
+#define MEVI_IVF_ASSIGN_ROWS 256
+#define MEVI_IVF_ASSIGN_COLS 128
+#define MEVI_IVF_ASSIGN_SPLIT_WGS 256
+#define MEVI_IVF_BUILD_MAX_NLIST 262144
+size_t mevi_ivf_assign_workspace_bytes(int64_t n, int64_t dim, int64_t nlist);
+int mevi_ivf_assign_f32(const float *x, int64_t n, int64_t dim, const float *centroids, int64_t nlist,
+                        int32_t *list_of, float *best_score, void *workspace, size_t workspace_bytes, void *stream);
+
+/* IVF-Flat build, step 2: labels -> the inverted lists mevi_ivf_scan_topk_f32 reads.
+ *   list_of i32 [n] (device): the list of every row;
+ *   list_offsets i64 [nlist + 1]: exclusive prefix sum of the list sizes; row_ids i64 [n]: the rows ordered by
+ *   (list, row) -- a stable sort by label, ids ascending inside a list; max_list_len i64 [1] (device): the longest list.
+ *   The list-major corpus is then mevi_gather_rows_f32(docs, row_ids).
+ *   A label outside [0, nlist) is never used as an index: its row is left out of every list, list_offsets[nlist] counts
+ *   the listed rows and row_ids beyond that count is not written.
+ *   A stable radix sort of (label, row) in tiles of MEVI_IVF_LISTS_TILE rows without atomics: no output bit depends on
+ *   scheduling.  Stream-ordered and graph-capturable like the call above.
+ *   Envelope: 1 <= nlist <= MEVI_IVF_BUILD_MAX_NLIST, 0 <= n < 2^31; n == 0 zeroes list_offsets and max_list_len.
+ *   mevi_ivf_build_lists_workspace_bytes: pure host arithmetic (16 n bytes + a table per tile), positive inside the
+ *   envelope, never smaller for a larger argument, 0 outside.
+ *   Refused before any launch, naming the argument: n negative, list_offsets / max_list_len null or not 8-byte aligned,
+ *   with n > 0 list_of / row_ids / workspace null, list_of not 4-byte, row_ids not 8-byte, workspace not 256-byte aligned
+ *   (MEVI_ERR_INVALID_ARG); nlist outside 1..262144, n >= 2^31 (MEVI_ERR_UNSUPPORTED); a workspace below
+ *   mevi_ivf_build_lists_workspace_bytes (MEVI_ERR_WORKSPACE; the message carries the needed size). */
+#define MEVI_IVF_LISTS_TILE 2048
+size_t mevi_ivf_build_lists_workspace_bytes(int64_t n, int64_t nlist);
+int mevi_ivf_build_lists(const int32_t *list_of, int64_t n, int64_t nlist, int64_t *list_offsets, int64_t *row_ids,
+                         int64_t *max_list_len, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Fine stage: the best k documents of a query's beam clusters (the running top-k of --knn_topk_by_step,
  * MEVI/main_models.py:3915-4014, 3919-3995), from beam keys to a fixed-shape top-k in one call.
  *   q f32, row stride ldq: [nq] rows (per_beam = 0) or [nq * R] rows (per_beam = 1: row b * R + j scores the candidates of

@@ -223,6 +223,73 @@ def ivf_scan_topk(query, docs, list_offsets, row_ids, max_list_len, probe, k, ou
     return out_s, out_i
 
 
+IVF_ASSIGN_ROWS = 256               # MEVI_IVF_ASSIGN_ROWS: rows a workgroup of `ivf_assign` keeps while it walks the centroids
+IVF_ASSIGN_COLS = 128               # MEVI_IVF_ASSIGN_COLS: centroids per tile of that walk (64 on grids too small for the device)
+IVF_ASSIGN_SPLIT_WGS = 256          # MEVI_IVF_ASSIGN_SPLIT_WGS: below this many row blocks the walk is split among workgroups
+IVF_BUILD_MAX_NLIST = 262144        # MEVI_IVF_BUILD_MAX_NLIST
+IVF_LISTS_TILE = 2048               # MEVI_IVF_LISTS_TILE: rows per workgroup of `ivf_build_lists`
+
+
+def ivf_assign_workspace_bytes(n, dim, nlist):
+    """Bytes of workspace `ivf_assign` needs (host arithmetic; 0 = shape outside the kernel's envelope)."""
+    return int(hip.lib().mevi_ivf_assign_workspace_bytes(n, dim, nlist))
+
+
+def ivf_build_lists_workspace_bytes(n, nlist):
+    """Bytes of workspace `ivf_build_lists` needs (host arithmetic; 0 = outside the envelope)."""
+    return int(hip.lib().mevi_ivf_build_lists_workspace_bytes(n, nlist))
+
+
+def ivf_assign(x, centroids, out=None, workspace=None):
+    """Nearest centroid by inner product per row (mevi_ivf_assign_f32): no [n, nlist] score matrix.
+
+    x f32 [n, dim], centroids f32 [nlist, dim].  Returns (list_of i32 [n], best_score f32 [n]): the lowest c that attains
+    max_c <x_r, centroid_c> (sequential fmaf chains, the bits of `ip_topk` and `ops.linear`) and that maximum.  `out` =
+    (list_of, best_score or None) and `workspace` (uint8, ivf_assign_workspace_bytes) preallocated: nothing is allocated."""
+    hip.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    assert centroids.is_cuda and centroids.dtype == torch.float32 and centroids.dim() == 2 and centroids.is_contiguous()
+    assert centroids.shape[1] == x.shape[1]
+    n, dim = x.shape
+    nlist = centroids.shape[0]
+    L = hip.lib()
+    if out is None:
+        out = (torch.empty(n, dtype=torch.int32, device=x.device), torch.empty(n, dtype=torch.float32, device=x.device))
+    list_of, best = out
+    assert list_of.dtype == torch.int32 and list_of.shape == (n,) and list_of.is_contiguous() and list_of.is_cuda
+    assert best is None or (best.dtype == torch.float32 and best.shape == (n,) and best.is_contiguous() and best.is_cuda)
+    if workspace is None and n:
+        workspace = torch.empty(L.mevi_ivf_assign_workspace_bytes(n, dim, nlist), dtype=torch.uint8, device=x.device)
+    with hip.device_guard(x.device):
+        st = L.mevi_ivf_assign_f32(hip.ptr(x), n, dim, hip.ptr(centroids), nlist, hip.ptr(list_of), None if best is None else hip.ptr(best),
+                                   hip.ptr(workspace) if workspace is not None and workspace.numel() else None,
+                                   0 if workspace is None else workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_ivf_assign_f32")
+    return list_of, best
+
+
+def ivf_build_lists(list_of, nlist, workspace=None):
+    """Labels -> inverted lists (mevi_ivf_build_lists): (list_offsets i64 [nlist + 1], row_ids i64 [n], max_list_len i64 [1]),
+    all on the device.  row_ids = the rows ordered by (list, row), i.e. torch.argsort(list_of, stable=True); a label outside
+    [0, nlist) leaves its row out: list_offsets[nlist] counts the listed rows, the slots of row_ids beyond it are not written."""
+    hip.require_gpu()
+    assert list_of.is_cuda and list_of.dtype == torch.int32 and list_of.dim() == 1 and list_of.is_contiguous()
+    n = list_of.numel()
+    dev = list_of.device
+    L = hip.lib()
+    offsets = torch.empty(nlist + 1, dtype=torch.int64, device=dev)
+    row_ids = torch.empty(n, dtype=torch.int64, device=dev)
+    longest = torch.empty(1, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(L.mevi_ivf_build_lists_workspace_bytes(n, nlist), dtype=torch.uint8, device=dev)
+    with hip.device_guard(dev):
+        st = L.mevi_ivf_build_lists(hip.ptr(list_of) if n else None, n, nlist, hip.ptr(offsets), hip.ptr(row_ids) if n else None,
+                                    hip.ptr(longest), hip.ptr(workspace) if workspace.numel() else None, workspace.numel(),
+                                    hip.stream_ptr())
+    hip.check(st, "mevi_ivf_build_lists")
+    return offsets, row_ids, longest
+
+
 def shard_range(n_rows, rank, world_size):
     """Contiguous row shard [start, end) of rank: ceil(n/world) rows each."""
     per = (n_rows + world_size - 1) // world_size

@@ -52,6 +52,10 @@ _SIGNATURES = {
     "mevi_ivf_scan_query_tile": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64]),
     "mevi_ivf_scan_topk_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                        c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mevi_ivf_assign_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "mevi_ivf_assign_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mevi_ivf_build_lists_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "mevi_ivf_build_lists": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mevi_fine_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "mevi_fine_topk_query_tile": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "mevi_fine_topk_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,

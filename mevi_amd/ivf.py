@@ -20,6 +20,12 @@ up to GRAPH_MAX_QUERIES queries can be captured and replayed as one graph (`sear
 earlier host loop (one exact search per probed list + a merge): same bits; it serves the shapes outside the scan's
 envelope, the regimes where it measured faster (scan_wanted: many query tiles over few long lists) and every shape when
 MEVI_IVF_SCAN=lists.
+
+The build (`train_centroids`, `IVFFlatIndex.__init__`) labels rows with mevi_ivf_assign_f32 -- the exact GEMM's loop with a running
+(best score, lowest index) per row instead of a stored score matrix -- and lays the lists out with mevi_ivf_build_lists (a stable
+sort of (label, row) on the device), both in csrc/ivf_build.hip.  MEVI_IVF_BUILD=host restores the torch composition they
+replaced (exact GEMM + argmax, argsort + bincount): same bits, the A/B partner of DESIGN 4.1g and the path of shapes outside the
+kernels' envelope.
 """
 import os
 import re
@@ -46,12 +52,49 @@ def parse_factory(param):
     return int(m.group(1)) if m else None
 
 
+def build_path():
+    """'device' (the kernels of csrc/ivf_build.hip) or 'host' (MEVI_IVF_BUILD=host: the torch composition they replaced --
+    exact GEMM + argmax, argsort + bincount -- unchanged: the A/B partner, and what shapes outside the envelope take)."""
+    return "host" if os.environ.get("MEVI_IVF_BUILD", "device") == "host" else "device"
+
+
+def assign_wanted(n, dim, nlist):
+    """True when `assign` takes mevi_ivf_assign_f32: not MEVI_IVF_BUILD=host and the shape is inside the kernel's envelope."""
+    return build_path() == "device" and n >= 1 and dense.ivf_assign_workspace_bytes(n, dim, nlist) > 0
+
+
 def assign(x, centroids, chunk=1 << 18):
     """argmax_c <x, centroid_c> per row (exact f32 chains; lowest c on ties) -> i32 [n]."""
+    if assign_wanted(x.shape[0], x.shape[1], centroids.shape[0]) and x.dtype == torch.float32 and centroids.dtype == torch.float32:
+        out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+        return dense.ivf_assign(x.contiguous(), centroids.contiguous(), out=(out, None))[0]
+    return assign_host(x, centroids, chunk)
+
+
+def assign_host(x, centroids, chunk=1 << 18):
+    """`assign` as the score matrix of the exact GEMM, chunk by chunk, and its argmax."""
     out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
     for a in range(0, x.shape[0], chunk):
         out[a:a + chunk] = torch.argmax(ops.linear(x[a:a + chunk].contiguous(), centroids), dim=1).to(torch.int32)
     return out
+
+
+def lists_wanted(n, nlist):
+    """True when `build_lists` takes mevi_ivf_build_lists: not MEVI_IVF_BUILD=host and the shape is inside its envelope."""
+    return build_path() == "device" and n >= 1 and dense.ivf_build_lists_workspace_bytes(n, nlist) > 0
+
+
+def build_lists(list_of, nlist):
+    """Labels -> (offsets i64 [nlist + 1] on the CPU, the same on the device, ids i64 [n]: the rows ordered by (list, row), the
+    longest list as an int).  The device path is one call; its offsets and longest list come back once (the scan's ABI wants
+    the latter on the host)."""
+    if lists_wanted(list_of.numel(), nlist):
+        offsets_dev, order, longest = dense.ivf_build_lists(list_of, nlist)
+        return offsets_dev.cpu(), offsets_dev, order, int(longest.item())
+    order = torch.argsort(list_of.long(), stable=True)                    # ids ascending inside a list
+    offsets = torch.zeros(nlist + 1, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(torch.bincount(list_of.long(), minlength=nlist), 0).cpu()
+    return offsets, offsets.to(list_of.device), order, (int((offsets[1:] - offsets[:-1]).max()) if nlist else 0)
 
 
 def train_centroids(docs, nlist, seed=1234):
@@ -84,13 +127,8 @@ class IVFFlatIndex:
         self.nlist = nlist
         self.centroids = train_centroids(docs, nlist, seed) if centroids is None else centroids.to(docs.device).contiguous()
         self.list_of = assign(docs, self.centroids)
-        order = torch.argsort(self.list_of.long(), stable=True)           # ids ascending inside a list
-        self.ids = order
-        self.docs = docs[order].contiguous()
-        self.offsets = torch.zeros(nlist + 1, dtype=torch.int64)
-        self.offsets[1:] = torch.cumsum(torch.bincount(self.list_of.long(), minlength=nlist), 0).cpu()
-        self.offsets_dev = self.offsets.to(docs.device)
-        self.max_list_len = int((self.offsets[1:] - self.offsets[:-1]).max()) if nlist else 0
+        self.offsets, self.offsets_dev, self.ids, self.max_list_len = build_lists(self.list_of, nlist)
+        self.docs = docs[self.ids].contiguous()
         self.centroid_offsets = torch.tensor([0, nlist], dtype=torch.int64, device=docs.device)   # the quantiser's one list
 
     def scan_wanted(self, nq, k, nprobe):

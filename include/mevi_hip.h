@@ -260,6 +260,10 @@ int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, in
                        float *out_score, int64_t *out_id, int32_t *out_ndoc,
                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same call with a multi-cluster merge and beam weights (FineStage.rerank's aggregate= and beam_weights= / doc_proba=):
+ * three more entry points under this prefix, with an `_agg` infix, declared and documented in mevi_hip_fine_agg.h. */
+#include "mevi_hip_fine_agg.h"
+
 /* ------------------------------------------------------------------------
  * Residual-quantisation encode: codes[n, M] (int32, values in [0, K)).
  * Replaces pq.get_rq_document_cluster / the index path of forward_rq with

@@ -16,6 +16,16 @@
 //            (score, ~id) keys, above that select_topk.h (histogram + radix select + id pass at the cut, as the IVF scan).
 //            A launch of 256 threads and 16 KiB of LDS takes the queries of up to 2048 places; when max_cand allows longer
 //            ones a second launch (1024 threads, up to 128 KiB) takes those, so a loose bound costs the short queries nothing.
+// mevi_fine_topk_agg_f32 is the same call with rerank's two other modes, both inside the last two launches:
+//   weights  (beam_weights, doc_proba) in the score step's epilogue: s = w[query][beam] * s, after the blend
+//            ratio * doc_proba[d] + (1 - ratio) * s when doc_proba is given -- each operation rounded on its own (__fmul_rn /
+//            __fadd_rn: no contraction), rerank's arithmetic.  With one row per query the beam of a place is the upper bound of
+//            the place in first[query][0..R].
+//   merge    (aggregate add / max) in the select step, fine_merge_select_kernel: the LDS sort on ~(id, place) keys, every run
+//            head folds its run's scores in walk order (from +0 by f32 adds, or from -inf by fmaxf), the keys are replaced IN
+//            PLACE by (score, ~id) of the heads and the empty key elsewhere -- every thread holds its places' new keys in
+//            registers across one barrier, so the second key set costs no LDS --, and the same sort orders the unique entries.
+//            Its envelope is the LDS sort's: max_cand <= 16384.  The same two launches share the queries by their places.
 // Nothing here reads a device value on the host: grids, LDS and the workspace follow from nq, R, k, dim and max_cand alone.
 // The only atomics are LDS integer counters; no result depends on their order of arrival.
 //
@@ -143,11 +153,17 @@ __global__ void __launch_bounds__(PLAN_THREADS) fine_plan_kernel(const int64_t *
 // ---- score ------------------------------------------------------------------------------------------------------------
 // Unit u = blockIdx.x: query u with the places [0, first[u][R]) (per_beam = 0) or beam j = u % R of query u / R with the
 // places [first[.][j], first[.][j + 1]) (per_beam = 1); either way its query row is q + u * ldq.
+// WEIGHTED: the occurrence's score is weights[query][beam] * s, s blended with doc_proba first when that is given; every
+// operation is one rounded f32 operation (no contraction), in rerank's order.
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(SCORE_THREADS) fine_score_kernel(const float *__restrict__ q, long long ldq, int per_beam, int R,
                                                                    const float *__restrict__ emb, int dim,
                                                                    const int32_t *__restrict__ cand_id,
                                                                    const int32_t *__restrict__ first, long long ld,
-                                                                   float *__restrict__ cand_score) {
+                                                                   float *__restrict__ cand_score,
+                                                                   const float *__restrict__ weights,
+                                                                   const float *__restrict__ doc_proba, float ratio,
+                                                                   float one_minus_ratio) {
   __shared__ __attribute__((aligned(16))) float sq[32];
   __shared__ __attribute__((aligned(16))) float sb[SCORE_THREADS / 64][64 * PD_LD];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -195,7 +211,26 @@ __global__ void __launch_bounds__(SCORE_THREADS) fine_score_kernel(const float *
       if (s + 1 < nslab) step(vb, qb, va, qa, s + 1);
     }
     const long long p = base + lane;
-    if (p < b) out[p] = acc + 0.0f;
+    if (p < b) {
+      float s = acc + 0.0f;
+      if (WEIGHTED) {
+        const int id = ids[p];
+        if (id >= 0) {                                  // a skipped id's score is never used
+          if (doc_proba) s = __fadd_rn(__fmul_rn(ratio, doc_proba[id]), __fmul_rn(one_minus_ratio, s));
+          int beam = j;
+          if (!per_beam) {                              // the last beam whose first place is not above p (f[0] = 0 <= p < f[R])
+            int hi = R;
+            while (hi - beam > 1) {
+              const int mid = (beam + hi) >> 1;
+              if (f[mid] <= p) beam = mid;
+              else hi = mid;
+            }
+          }
+          s = __fmul_rn(weights[(size_t)qi * R + beam], s);
+        }
+      }
+      out[p] = s;
+    }
   }
 }
 
@@ -252,6 +287,76 @@ __global__ void __launch_bounds__(NT) fine_select_kernel(const float *__restrict
   }
 }
 
+// The selection with documents merged (aggregate 1 add, 2 max): the entries of one id become one.  The same split of the
+// queries over two launches, ITEMS = places of a thread = the launch's most places / NT.
+//   sort 1   descending on ~(id, place): ascending (id, place), so a run of one id stands in walk order; a skipped id and the
+//            padding are the empty key and sort last -- the nsel[q] counted entries come first.
+//   fold     the thread of a run's first place folds the run: scores are read by place from cand_score.
+//   re-key   in place: every thread computes the new keys of its places (the head's (score, ~id), else empty) into registers,
+//            one barrier, then stores them -- no thread reads a key another has already replaced.
+//   sort 2   descending on (score, ~id); the first k are the output, the unique count goes to out_nuniq.
+template <int NT, int ITEMS>
+__global__ void __launch_bounds__(NT) fine_merge_select_kernel(const float *__restrict__ cand_score,
+                                                               const int32_t *__restrict__ cand_id, long long ld,
+                                                               const int32_t *__restrict__ nslot, const int32_t *__restrict__ nsel,
+                                                               int n_lo, int k, int mode, float *__restrict__ out_s,
+                                                               int64_t *__restrict__ out_i, int32_t *__restrict__ out_nuniq) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long skeys[];
+  __shared__ int s_nuniq;
+  const int q = blockIdx.x, t = threadIdx.x;
+  const int n = nslot[q];
+  if (n < n_lo || (n_lo == 0 && n > FINE_SMALL_MAX)) return;   // the other launch's query
+  const int nv = nsel[q];                               // entries with an id inside [0, n_docs) among the n places
+  const float *sc = cand_score + (size_t)q * (size_t)ld;
+  const int32_t *ids = cand_id + (size_t)q * (size_t)ld;
+  int P = 64;
+  while (P < n) P <<= 1;                                // n <= NT * ITEMS: the host refuses a merge above FINE_SORT_MAX places
+  for (int i = t; i < P; i += NT) {
+    const int id = i < n ? ids[i] : -1;
+    skeys[i] = id >= 0 ? ~(((unsigned long long)(uint32_t)id << 32) | (unsigned long long)(uint32_t)i) : 0ull;
+  }
+  if (t == 0) s_nuniq = 0;
+  __syncthreads();
+  bitonic_sort_desc<NT>(skeys, P, t);
+  unsigned long long fresh[ITEMS];
+  int heads = 0;
+#pragma unroll
+  for (int u = 0; u < ITEMS; ++u) {
+    const int i = t + u * NT;
+    fresh[u] = 0ull;
+    if (i < nv) {
+      const uint32_t id = (uint32_t)(~skeys[i] >> 32);
+      if (i == 0 || (uint32_t)(~skeys[i - 1] >> 32) != id) {
+        float agg = mode == 1 ? 0.f : -INFINITY;
+        for (int r = i; r < nv; ++r) {
+          const unsigned long long kr = ~skeys[r];
+          if ((uint32_t)(kr >> 32) != id) break;
+          const float s = sc[(uint32_t)kr];
+          agg = mode == 1 ? __fadd_rn(agg, s) : fmaxf(agg, s);
+        }
+        fresh[u] = make_key(agg, id);
+        ++heads;
+      }
+    }
+  }
+  __syncthreads();                                      // every old key has been read
+#pragma unroll
+  for (int u = 0; u < ITEMS; ++u) {
+    const int i = t + u * NT;
+    if (i < P) skeys[i] = fresh[u];
+  }
+  if (heads) atomicAdd(&s_nuniq, heads);
+  __syncthreads();
+  bitonic_sort_desc<NT>(skeys, P, t);
+  for (int i = t; i < k; i += NT) {
+    const unsigned long long key = i < P ? skeys[i] : 0ull;
+    out_s[(size_t)q * k + i] = key ? key_score(key) : -FLT_MAX;
+    out_i[(size_t)q * k + i] = key ? (int64_t)key_id(key) : -1;
+  }
+  if (t == 0) out_nuniq[q] = s_nuniq;
+}
+static_assert(256 * 8 == FINE_SMALL_MAX && 1024 * 16 == FINE_SORT_MAX, "fine_merge_select_kernel: ITEMS * NT covers the launch's places");
+
 // LDS of a selection launch whose queries have at most `most` places: the sort's keys; 128 KiB above 8192 places, which is
 // room for select_topk's 40 KiB too.
 size_t select_lds_bytes(int64_t most) {
@@ -265,6 +370,12 @@ size_t select_lds_bytes(int64_t most) {
 
 using namespace mevi;
 
+// The merge holds a query's places in the LDS sort: inside fine_plan's envelope, and with aggregate 1 / 2 up to FINE_SORT_MAX.
+static bool fine_agg_plan(int64_t nq, int64_t R, int64_t k, int64_t dim, int64_t max_cand, int aggregate, FinePlan &p) {
+  if (aggregate < 0 || aggregate > 2 || (aggregate != 0 && max_cand > FINE_SORT_MAX)) return false;
+  return fine_plan(nq, R, k, dim, max_cand, p);
+}
+
 extern "C" size_t mevi_fine_topk_workspace_bytes(int64_t nq, int64_t R, int64_t k, int64_t dim, int64_t max_cand) {
   FinePlan p;
   return fine_plan(nq, R, k, dim, max_cand, p) ? p.total : 0;
@@ -275,20 +386,39 @@ extern "C" int64_t mevi_fine_topk_query_tile(int64_t nq, int64_t R, int64_t k, i
   return fine_plan(nq, R, k, dim, max_cand, p) ? p.qt : 0;
 }
 
-extern "C" int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, int64_t R, const float *emb,
-                                  int64_t n_docs, int64_t dim, const int64_t *cluster_keys, const int64_t *cluster_offsets,
-                                  const int64_t *cluster_docs, int64_t n_clusters, const int64_t *beam_keys, int64_t max_cand,
-                                  int64_t k, float *out_score, int64_t *out_id, int32_t *out_ndoc, void *workspace,
-                                  size_t workspace_bytes, void *stream) {
+extern "C" size_t mevi_fine_topk_agg_workspace_bytes(int64_t nq, int64_t R, int64_t k, int64_t dim, int64_t max_cand,
+                                                     int aggregate) {
+  FinePlan p;
+  return fine_agg_plan(nq, R, k, dim, max_cand, aggregate, p) ? p.total : 0;
+}
+
+extern "C" int64_t mevi_fine_topk_agg_query_tile(int64_t nq, int64_t R, int64_t k, int64_t dim, int64_t max_cand, int aggregate) {
+  FinePlan p;
+  return fine_agg_plan(nq, R, k, dim, max_cand, aggregate, p) ? p.qt : 0;
+}
+
+extern "C" int mevi_fine_topk_agg_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, int64_t R, const float *emb,
+                                      int64_t n_docs, int64_t dim, const int64_t *cluster_keys, const int64_t *cluster_offsets,
+                                      const int64_t *cluster_docs, int64_t n_clusters, const int64_t *beam_keys, int64_t max_cand,
+                                      int64_t k, int aggregate, const float *beam_weights, const float *doc_proba, float ratio,
+                                      float one_minus_ratio, float *out_score, int64_t *out_id, int32_t *out_ndoc,
+                                      int32_t *out_nuniq, void *workspace, size_t workspace_bytes, void *stream) {
   MEVI_REQUIRE(nq >= 0 && n_docs >= 0 && n_clusters >= 0 && dim >= 1 && (per_beam == 0 || per_beam == 1), MEVI_ERR_INVALID_ARG,
                "fine_topk: bad shape nq=%lld n_docs=%lld n_clusters=%lld dim=%lld per_beam=%d", (long long)nq, (long long)n_docs,
                (long long)n_clusters, (long long)dim, per_beam);
+  MEVI_REQUIRE(aggregate >= 0 && aggregate <= 2, MEVI_ERR_INVALID_ARG, "fine_topk: aggregate=%d outside 0..2 (none, add, max)",
+               aggregate);
+  MEVI_REQUIRE(!doc_proba || beam_weights, MEVI_ERR_INVALID_ARG,
+               "fine_topk: doc_proba without beam_weights (the document probability is blended in under the beam weights only)");
   MEVI_REQUIRE(dim % 4 == 0, MEVI_ERR_UNSUPPORTED, "fine_topk: dim=%lld is no multiple of 4 (rows are read as float4)",
                (long long)dim);
   MEVI_REQUIRE(k >= 1 && k <= FINE_MAX_K, MEVI_ERR_UNSUPPORTED, "fine_topk: k=%lld outside 1..%d", (long long)k, FINE_MAX_K);
   MEVI_REQUIRE(R >= 1 && R <= FINE_MAX_R, MEVI_ERR_UNSUPPORTED, "fine_topk: R=%lld outside 1..%d", (long long)R, FINE_MAX_R);
   MEVI_REQUIRE(n_docs <= 0x7fffffffLL, MEVI_ERR_UNSUPPORTED, "fine_topk: n_docs=%lld: ids must fit 31 bits", (long long)n_docs);
   MEVI_REQUIRE(max_cand >= 1, MEVI_ERR_INVALID_ARG, "fine_topk: max_cand=%lld below 1", (long long)max_cand);
+  MEVI_REQUIRE(aggregate == 0 || max_cand <= FINE_SORT_MAX, MEVI_ERR_UNSUPPORTED,
+               "fine_topk: max_cand=%lld above the %d places the merge (aggregate=%d) sorts in LDS", (long long)max_cand,
+               FINE_SORT_MAX, aggregate);
   MEVI_REQUIRE(ldq >= dim && ldq % 4 == 0, MEVI_ERR_INVALID_ARG, "fine_topk: ldq=%lld below dim=%lld or no multiple of 4",
                (long long)ldq, (long long)dim);
   FinePlan p;
@@ -298,6 +428,7 @@ extern "C" int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int
   if (nq == 0) return MEVI_OK;
   MEVI_REQUIRE(q && emb && beam_keys && out_score && out_id && out_ndoc, MEVI_ERR_INVALID_ARG,
                "fine_topk: null pointer (q, emb, beam_keys, out_score, out_id, out_ndoc)");
+  MEVI_REQUIRE(aggregate == 0 || out_nuniq, MEVI_ERR_INVALID_ARG, "fine_topk: null pointer (out_nuniq with aggregate=%d)", aggregate);
   MEVI_REQUIRE(n_clusters == 0 || (cluster_keys && cluster_offsets && cluster_docs), MEVI_ERR_INVALID_ARG,
                "fine_topk: null pointer (cluster_keys, cluster_offsets, cluster_docs with n_clusters=%lld)", (long long)n_clusters);
   MEVI_REQUIRE(((uintptr_t)q | (uintptr_t)emb) % 16 == 0, MEVI_ERR_INVALID_ARG, "fine_topk: q / emb not 16-byte aligned");
@@ -306,6 +437,8 @@ extern "C" int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int
                MEVI_ERR_INVALID_ARG,
                "fine_topk: misaligned pointer (cluster_keys / cluster_offsets / cluster_docs / beam_keys / out_id 8 bytes, "
                "out_score / out_ndoc 4)");
+  MEVI_REQUIRE(((uintptr_t)beam_weights | (uintptr_t)doc_proba | (uintptr_t)out_nuniq) % 4 == 0, MEVI_ERR_INVALID_ARG,
+               "fine_topk: misaligned pointer (beam_weights / doc_proba / out_nuniq 4 bytes)");
   MEVI_REQUIRE(workspace && (uintptr_t)workspace % 256 == 0, MEVI_ERR_INVALID_ARG,
                "fine_topk: workspace null or not 256-byte aligned");
   MEVI_REQUIRE(workspace_bytes >= p.total, MEVI_ERR_WORKSPACE, "fine_topk: workspace of %zu bytes, %zu needed", workspace_bytes,
@@ -319,7 +452,8 @@ extern "C" int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int
   const size_t lds_small = select_lds_bytes(max_cand < FINE_SMALL_MAX ? max_cand : FINE_SMALL_MAX), lds_wide = select_lds_bytes(max_cand);
   const bool wide = max_cand > FINE_SMALL_MAX;          // a query may be long: the second selection launch
   if (wide && lds_wide > 65536)
-    MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(fine_select_kernel<1024>),
+    MEVI_HIP_CHECK(hipFuncSetAttribute(aggregate ? reinterpret_cast<const void *>(fine_merge_select_kernel<1024, 16>)
+                                                 : reinterpret_cast<const void *>(fine_select_kernel<1024>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wide));
   const int64_t row_scale = per_beam ? R : 1;           // query rows per query
   for (int64_t q0 = 0; q0 < nq; q0 += p.qt) {
@@ -332,14 +466,40 @@ extern "C" int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int
     int64_t chunks = (max_cand + SCORE_THREADS - 1) / SCORE_THREADS;
     const int64_t room = SCORE_MAX_GRID / units > 1 ? SCORE_MAX_GRID / units : 1;
     if (chunks > room) chunks = room;
-    fine_score_kernel<<<dim3((unsigned)units, (unsigned)chunks), SCORE_THREADS, 0, st>>>(
-        q + q0 * row_scale * ldq, (long long)ldq, per_beam, (int)R, emb, (int)dim, cand_id, first, (long long)p.ld, cand_score);
-    fine_select_kernel<256><<<qn, 256, lds_small, st>>>(cand_score, cand_id, (long long)p.ld, nslot, nsel, 0, (int)k,
-                                                        out_score + q0 * k, out_id + q0 * k);
-    if (wide)
-      fine_select_kernel<1024><<<qn, 1024, lds_wide, st>>>(cand_score, cand_id, (long long)p.ld, nslot, nsel, FINE_SMALL_MAX + 1,
-                                                           (int)k, out_score + q0 * k, out_id + q0 * k);
+    const dim3 score_grid((unsigned)units, (unsigned)chunks);
+    if (beam_weights)
+      fine_score_kernel<true><<<score_grid, SCORE_THREADS, 0, st>>>(q + q0 * row_scale * ldq, (long long)ldq, per_beam, (int)R, emb,
+                                                                    (int)dim, cand_id, first, (long long)p.ld, cand_score,
+                                                                    beam_weights + q0 * R, doc_proba, ratio, one_minus_ratio);
+    else
+      fine_score_kernel<false><<<score_grid, SCORE_THREADS, 0, st>>>(q + q0 * row_scale * ldq, (long long)ldq, per_beam, (int)R, emb,
+                                                                     (int)dim, cand_id, first, (long long)p.ld, cand_score, nullptr,
+                                                                     nullptr, 0.f, 0.f);
+    float *os = out_score + q0 * k;
+    int64_t *oi = out_id + q0 * k;
+    if (aggregate) {
+      fine_merge_select_kernel<256, 8><<<qn, 256, lds_small, st>>>(cand_score, cand_id, (long long)p.ld, nslot, nsel, 0, (int)k,
+                                                                   aggregate, os, oi, out_nuniq + q0);
+      if (wide)
+        fine_merge_select_kernel<1024, 16><<<qn, 1024, lds_wide, st>>>(cand_score, cand_id, (long long)p.ld, nslot, nsel,
+                                                                       FINE_SMALL_MAX + 1, (int)k, aggregate, os, oi, out_nuniq + q0);
+    } else {
+      fine_select_kernel<256><<<qn, 256, lds_small, st>>>(cand_score, cand_id, (long long)p.ld, nslot, nsel, 0, (int)k, os, oi);
+      if (wide)
+        fine_select_kernel<1024><<<qn, 1024, lds_wide, st>>>(cand_score, cand_id, (long long)p.ld, nslot, nsel, FINE_SMALL_MAX + 1,
+                                                             (int)k, os, oi);
+    }
   }
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;
+}
+
+extern "C" int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, int64_t R, const float *emb,
+                                  int64_t n_docs, int64_t dim, const int64_t *cluster_keys, const int64_t *cluster_offsets,
+                                  const int64_t *cluster_docs, int64_t n_clusters, const int64_t *beam_keys, int64_t max_cand,
+                                  int64_t k, float *out_score, int64_t *out_id, int32_t *out_ndoc, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  return mevi_fine_topk_agg_f32(q, ldq, per_beam, nq, R, emb, n_docs, dim, cluster_keys, cluster_offsets, cluster_docs, n_clusters,
+                                beam_keys, max_cand, k, 0, nullptr, nullptr, 0.f, 0.f, out_score, out_id, out_ndoc, nullptr,
+                                workspace, workspace_bytes, stream);
 }

@@ -13,7 +13,8 @@ sort.  Order: score descending, ties by ascending doc id (torch.sort leaves ties
 
 `FineStage.topk` / `topk_graph` are the same stage as ONE stream-ordered device call (mevi_fine_topk_f32, csrc/fine_topk.hip):
 beam keys on the device -> per query the best k documents and ndoc, nothing copied to the host.  New surface: `rerank` and its
-callers are untouched, and nothing is routed through it by default.
+callers are untouched, and nothing is routed through it by default.  With `aggregate=` / `beam_weights=` / `doc_proba=` the
+call is mevi_fine_topk_agg_f32: rerank's multi-cluster merge (up to MAX_SEGMENT candidates of a query) and topic weights.
 """
 import numpy as np
 import torch
@@ -200,24 +201,53 @@ class FineStage:
             self._key_weights = torch.tensor([self.index.K ** (M - 1 - j) for j in range(M)], dtype=torch.int64, device=self.dev)
         return (beam.to(torch.int64) * self._key_weights).sum(-1)
 
-    def topk(self, query_emb, beam, k, out=None, workspace=None, max_cand=None):
+    def topk(self, query_emb, beam, k, out=None, workspace=None, max_cand=None, aggregate=None, beam_weights=None, doc_proba=None,
+             ratio=0.0):
         """The best k documents of every query's beam clusters, without a host copy: (scores f32 [B, k], ids i64 [B, k],
         ndoc i32 [B]) on the device; the first k entries of `rerank`'s lists, bit for bit, padded with -FLT_MAX / -1, and its
         ndoc.  query_emb f32 [B, dim], or [B * R, dim] for per-beam embeddings (as `rerank` infers it); `beam`: codes
         [B, R, M] or keys i64 [B, R] on the device.  One mevi_fine_topk_f32 call on the current stream.  `max_cand`: the bound on
-        one query's candidates when `max_candidates(R)` is not one (rows that repeat a key)."""
+        one query's candidates when `max_candidates(R)` is not one (rows that repeat a key).
+
+        aggregate 'add' | 'max', beam_weights f32 [B, R] (device), doc_proba f32 [N] (device) with ratio: `rerank`'s arguments
+        of those names, in one mevi_fine_topk_agg_f32 call.  With any of them set the result is (scores, ids, ndoc, nuniq):
+        nuniq i32 [B] is the number of unique documents that competed -- the length of `rerank`'s list; padding starts after
+        it -- and None without `aggregate`.  The merge sorts a query's candidates in LDS: above MAX_SEGMENT candidates it
+        raises a ValueError (use `rerank`, whose device-wide sorts take any length).  Not built here: the `beam_recon` form
+        (per-(document, cluster) probabilities of --doc_multiclus > 1 with a ratio > 0).  `rerank` and the CLIs do not go
+        through this call."""
         keys = self.beam_keys(beam)
         bound = self.max_candidates(keys.shape[1]) if max_cand is None else int(max_cand)
-        return ops.fine_topk(query_emb, self.emb, *self._device_index(), keys, bound, k, out=out, workspace=workspace)
+        if aggregate is None and beam_weights is None and doc_proba is None:
+            return ops.fine_topk(query_emb, self.emb, *self._device_index(), keys, bound, k, out=out, workspace=workspace)
+        if aggregate not in (None, "add", "max"):
+            raise ValueError(aggregate)
+        if aggregate is not None and bound > MAX_SEGMENT:
+            raise ValueError(f"topk: aggregate={aggregate!r} merges at most {MAX_SEGMENT} candidates of a query in LDS and the bound "
+                             f"is {bound}: take `rerank` for this index")
+        if beam_weights is not None:
+            beam_weights = torch.as_tensor(beam_weights, dtype=torch.float32, device=self.dev)
+        return ops.fine_topk(query_emb, self.emb, *self._device_index(), keys, bound, k, out=out, workspace=workspace,
+                             aggregate=aggregate, beam_weights=beam_weights, doc_proba=doc_proba, ratio=ratio)
 
-    def topk_graph(self, B, R, k, per_beam=False):
+    def topk_graph(self, B, R, k, per_beam=False, aggregate=None, weighted=False, doc_proba=None, ratio=0.0):
         """A captured graph of `topk` for exactly B <= TOPK_GRAPH_MAX_QUERIES queries of R beams:
-        `.run(query_emb, beam_keys)` -> (scores, ids, ndoc)."""
+        `.run(query_emb, beam_keys)` -> (scores, ids, ndoc).  With `aggregate`, `weighted` or `doc_proba` (fixed at capture, with
+        `ratio`) the graph holds `topk`'s call of those modes: `.run(query_emb, beam_keys, beam_weights)` copies the weights into
+        a static buffer and returns (scores, ids, ndoc, nuniq)."""
         if not 1 <= B <= TOPK_GRAPH_MAX_QUERIES:
             raise ValueError(f"topk_graph: B={B} outside 1..{TOPK_GRAPH_MAX_QUERIES}")
-        if ops.fine_topk_workspace_bytes(B, R, k, self.emb.shape[1], self.max_candidates(R)) < 1:
+        if aggregate not in (None, "add", "max"):
+            raise ValueError(aggregate)
+        if doc_proba is not None and not weighted:
+            raise ValueError("topk_graph: doc_proba is read under beam weights only (weighted=True)")
+        bound = self.max_candidates(R)
+        if aggregate is not None and bound > MAX_SEGMENT:
+            raise ValueError(f"topk_graph: aggregate={aggregate!r} merges at most {MAX_SEGMENT} candidates of a query in LDS and the "
+                             f"bound is {bound}: take `rerank` for this index")
+        if ops.fine_topk_agg_workspace_bytes(B, R, k, self.emb.shape[1], bound, aggregate) < 1:
             raise ValueError(f"topk_graph: B={B} R={R} k={k} is outside the envelope of mevi_fine_topk_f32")
-        return TopkGraph(self, B, R, k, per_beam)
+        return TopkGraph(self, B, R, k, per_beam, aggregate, weighted, doc_proba, ratio)
 
     def gt_scores(self, query_emb, gt_doc_ids):
         """q . emb[gt] for the hard-negative log line (main_models.py:4024-4045): list of f32 arrays."""
@@ -231,28 +261,38 @@ class FineStage:
 
 
 class TopkGraph:
-    """`FineStage.topk` of a fixed (B, R, k, per_beam) as one replayed graph: static query, key and output buffers and the
-    workspace are allocated here, the first call runs eagerly (it loads the kernels), the second is captured."""
+    """`FineStage.topk` of a fixed (B, R, k, per_beam, aggregate, weighted, doc_proba, ratio) as one replayed graph: static
+    query, key, weight and output buffers and the workspace are allocated here, the first call runs eagerly (it loads the
+    kernels), the second is captured."""
 
-    def __init__(self, stage, B, R, k, per_beam):
+    def __init__(self, stage, B, R, k, per_beam, aggregate=None, weighted=False, doc_proba=None, ratio=0.0):
         dev, dim = stage.dev, stage.emb.shape[1]
         self.query = torch.zeros((B * R if per_beam else B, dim), dtype=torch.float32, device=dev)
         self.keys = torch.full((B, R), -1, dtype=torch.int64, device=dev)
+        self.weights = torch.zeros((B, R), dtype=torch.float32, device=dev) if weighted else None
         out = (torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int64, device=dev),
                torch.empty((B,), dtype=torch.int32, device=dev))
-        ws = torch.empty(ops.fine_topk_workspace_bytes(B, R, k, dim, stage.max_candidates(R)), dtype=torch.uint8, device=dev)
-        stage.topk(self.query, self.keys, k, out=out, workspace=ws)
+        kw = {}
+        if aggregate is not None or weighted:
+            out += (torch.empty((B,), dtype=torch.int32, device=dev) if aggregate is not None else None,)
+            kw = dict(aggregate=aggregate, beam_weights=self.weights, doc_proba=doc_proba, ratio=ratio)
+        ws = torch.empty(ops.fine_topk_agg_workspace_bytes(B, R, k, dim, stage.max_candidates(R), aggregate), dtype=torch.uint8,
+                         device=dev)
+        stage.topk(self.query, self.keys, k, out=out, workspace=ws, **kw)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = stage.topk(self.query, self.keys, k, out=out, workspace=ws)
-        self.stage, self.workspace = stage, ws             # the graph holds their addresses
+            self.out = stage.topk(self.query, self.keys, k, out=out, workspace=ws, **kw)
+        self.stage, self.workspace, self.doc_proba = stage, ws, doc_proba      # the graph holds their addresses
 
-    def run(self, query_emb, beam_keys):
+    def run(self, query_emb, beam_keys, beam_weights=None):
+        assert (beam_weights is not None) == (self.weights is not None), "beam_weights go with a graph captured weighted=True"
         self.query.copy_(query_emb)
         self.keys.copy_(beam_keys)
+        if beam_weights is not None:
+            self.weights.copy_(torch.as_tensor(beam_weights, dtype=torch.float32))
         self.graph.replay()
-        return tuple(o.clone() for o in self.out)
+        return tuple(None if o is None else o.clone() for o in self.out)
 
 
 def coarse_ranks(beam_codes, gt_codes):

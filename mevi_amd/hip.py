@@ -171,9 +171,19 @@ _SIGNATURES = {
 }
 
 
-def exported_symbols():
-    """Names every entry point include/mevi_hip.h declares."""
-    return sorted(_SIGNATURES)
+# include/mevi_hip_fine_agg.h (included by mevi_hip.h): the fine stage's call with merge and weights
+_FINE_AGG_SIGNATURES = {
+    "mevi_fine_topk_agg_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "mevi_fine_topk_agg_query_tile": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "mevi_fine_topk_agg_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_float, c_float,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
+
+def exported_symbols(header="mevi_hip.h"):
+    """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h, which it includes)."""
+    return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES}[header])
 
 
 def lib():
@@ -184,7 +194,7 @@ def lib():
                 f"{LIB} not found: build it with `python -m mevi_amd.build` "
                 "(or __graft_entry__.build()); mevi_amd has no CPU fallback")
         L = ctypes.CDLL(LIB)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

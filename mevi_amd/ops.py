@@ -829,17 +829,44 @@ def fine_topk_query_tile(nq, R, k, dim, max_cand):
     return int(hip.lib().mevi_fine_topk_query_tile(nq, R, k, dim, max_cand))
 
 
+FINE_AGGREGATE = {None: 0, "add": 1, "max": 2}       # the `aggregate` argument of mevi_fine_topk_agg_f32
+
+
+def fine_topk_agg_workspace_bytes(nq, R, k, dim, max_cand, aggregate=None):
+    """Bytes of workspace `fine_topk` needs with `aggregate` (None, 'add', 'max'); 0 = outside the envelope, which under a merge
+    ends at FINE_TOPK_SORT_MAX candidates."""
+    return int(hip.lib().mevi_fine_topk_agg_workspace_bytes(nq, R, k, dim, max_cand, FINE_AGGREGATE[aggregate]))
+
+
+def fine_topk_agg_query_tile(nq, R, k, dim, max_cand, aggregate=None):
+    """Queries per tile of `fine_topk` with `aggregate` (0 = outside the envelope)."""
+    return int(hip.lib().mevi_fine_topk_agg_query_tile(nq, R, k, dim, max_cand, FINE_AGGREGATE[aggregate]))
+
+
 @hip.on_device
-def fine_topk(query, emb, cluster_keys, cluster_offsets, cluster_docs, beam_keys, max_cand, k, out=None, workspace=None):
-    """The best k documents of every query's beam clusters (mevi_fine_topk_f32).
+def fine_topk(query, emb, cluster_keys, cluster_offsets, cluster_docs, beam_keys, max_cand, k, out=None, workspace=None,
+              aggregate=None, beam_weights=None, doc_proba=None, ratio=0.0):
+    """The best k documents of every query's beam clusters (mevi_fine_topk_f32; with any of the last four arguments
+    mevi_fine_topk_agg_f32).
 
     query f32 [B, dim] or [B * R, dim] (row b * R + j scores beam j of query b), last dim contiguous; emb f32 [N, dim];
     cluster_keys / cluster_offsets / cluster_docs i64 on the device: the CSR arrays of rq.ClusterIndex (all None: no cluster);
     beam_keys i64 [B, R]; max_cand: host-known bound on one query's candidates.
     Returns (scores f32 [B, k] desc, ids i64 [B, k], ndoc i32 [B]; ties by ascending id; -FLT_MAX / -1 padding).
     Stream-ordered: with `out` = (scores, ids, ndoc) and `workspace` (uint8, fine_topk_workspace_bytes) preallocated nothing
-    is allocated either."""
+    is allocated either.
+
+    aggregate 'add' | 'max', beam_weights f32 [B, R], doc_proba f32 [N] with ratio: `FineStage.rerank`'s arguments of those
+    names, on the device.  A document reached through several beam clusters is listed once, its scores folded in walk order
+    (sequential f32 adds from +0, or the maximum); an occurrence's score is its beam's weight times q.d, or, with doc_proba and
+    a non-zero ratio, times ratio * doc_proba[d] + (1 - ratio) * q.d (every operation a rounded f32 operation).  With any of
+    them the result is (scores, ids, ndoc, nuniq): nuniq i32 [B] counts the unique documents that competed (None without
+    `aggregate`), padding starts after it, and `out` is the 4-tuple.  Out of scope: rerank's `beam_recon` form, and a merge
+    of more than FINE_TOPK_SORT_MAX candidates (fine_topk_agg_workspace_bytes is 0 there; the call is refused)."""
     hip.require_gpu()
+    if aggregate not in FINE_AGGREGATE:
+        raise ValueError(aggregate)
+    extended = aggregate is not None or beam_weights is not None or doc_proba is not None
     query, rows, dim, ldq = _rows2d(_f32(query))
     if rows == 1:
         ldq = dim                                      # a single row's stride is arbitrary (numpy hands over 0)
@@ -861,10 +888,39 @@ def fine_topk(query, emb, cluster_keys, cluster_offsets, cluster_docs, beam_keys
     if out is None:
         out = (torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int64, device=dev),
                torch.empty((B,), dtype=torch.int32, device=dev))
-    out_s, out_i, out_n = out
+        if extended:
+            out += (torch.empty((B,), dtype=torch.int32, device=dev) if aggregate is not None else None,)
+    out_s, out_i, out_n = out[:3]
     assert out_s.shape == (B, k) and out_i.shape == (B, k) and out_n.shape == (B,)
     assert out_s.is_contiguous() and out_i.is_contiguous() and out_n.is_contiguous()
     L = hip.lib()
+    if extended:
+        assert len(out) == 4
+        out_u = out[3]
+        if aggregate is not None:
+            assert out_u is not None and out_u.shape == (B,) and out_u.dtype == torch.int32 and out_u.is_contiguous()
+        else:
+            out_u = None
+        if beam_weights is not None:
+            beam_weights = _f32(beam_weights)
+            assert beam_weights.is_cuda and beam_weights.shape == (B, R) and beam_weights.is_contiguous()
+        if doc_proba is not None and ratio:
+            doc_proba = _f32(doc_proba)
+            assert doc_proba.is_cuda and doc_proba.shape == (emb.shape[0],) and doc_proba.is_contiguous()
+        elif beam_weights is not None:
+            doc_proba = None                            # as rerank: the blend takes a non-zero ratio
+        if workspace is None:
+            need = L.mevi_fine_topk_agg_workspace_bytes(B, R, k, dim, max_cand, FINE_AGGREGATE[aggregate])
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        st = L.mevi_fine_topk_agg_f32(hip.ptr(query), ldq, per_beam, B, R, hip.ptr(emb), emb.shape[0], dim,
+                                      *(None if a is None else hip.ptr(a) for a in csr), n_clusters, hip.ptr(beam_keys),
+                                      int(max_cand), k, FINE_AGGREGATE[aggregate],
+                                      *(None if a is None else hip.ptr(a) for a in (beam_weights, doc_proba)), float(ratio),
+                                      1.0 - float(ratio), hip.ptr(out_s), hip.ptr(out_i), hip.ptr(out_n),
+                                      None if out_u is None else hip.ptr(out_u),
+                                      hip.ptr(workspace) if workspace.numel() else None, workspace.numel(), hip.stream_ptr())
+        hip.check(st, "mevi_fine_topk_agg_f32")
+        return out_s, out_i, out_n, out_u
     if workspace is None:
         workspace = torch.empty(L.mevi_fine_topk_workspace_bytes(B, R, k, dim, max_cand), dtype=torch.uint8, device=dev)
     st = L.mevi_fine_topk_f32(hip.ptr(query), ldq, per_beam, B, R, hip.ptr(emb), emb.shape[0], dim,

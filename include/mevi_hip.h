@@ -662,6 +662,33 @@ int mevi_rq_neg_dist_f32(const float *x, int64_t n, int64_t dim, const float *ce
 int mevi_gather_sub_f32(const float *x, const int64_t *src, const float *centroids, const int32_t *code,
                         int64_t n, int64_t dim, float *out, void *stream);
 
+/* pq.beam_search in one stream-ordered call (csrc/rq_beam.hip): the top-R code paths of every row,
+ *   labels i32 [n, R, M] and proba f32 [n, R] (may be null), bit for bit what the composition above returns
+ *   (mevi_rq_neg_dist_f32 -> mevi_beam_step_f32(final_step = 2) or mevi_row_softmax_f32(mode 1) -> mevi_gather_sub_f32,
+ *   level after level) -- without the [n * R, dim] residuals or the [n * nb, K] score rows ever reaching memory.
+ *   pq == 0: x f32 [n, dim], codebook f32 [M, K, dim]; the level-j score row of a beam is -sum_k fmaf(r_k - c_k, r_k - c_k, .),
+ *     k ascending, of its own residual r = ((x - C[0][c0]) - C[1][c1]) - ... (one f32 subtraction per element and level).
+ *   pq == 1: codebook f32 [M, K, dsub], dsub = dim / M; level j scores x[:, j * dsub : (j + 1) * dsub], read in place, the
+ *     same row for every beam.
+ *   Per row: m = max, s = sum of expf(v - m) (per-lane partial sums over c = lane, lane + 64, ..., then the xor butterfly
+ *   32 .. 1), p = expf(v - m) / expf(logf(s)); candidate = beam_prob * p (beam_prob = 1.0f at level 0).  With nb beams
+ *   entering a level: R < nb * K keeps the R largest candidates in descending order, ties to the lower beam * K + code;
+ *   otherwise (R == nb * K included) every candidate is kept in (beam, code) order.  A beam's label row is its parent's
+ *   row plus the new code.  Rows with non-finite scores: unspecified.
+ * Envelope: 1 <= M <= 8, 1 <= K <= 256 (any value), 1 <= R <= 16, R <= K^M, dim % 4 == 0, 4 <= dim <= 4096, for pq also
+ *   dim % M == 0 and dsub % 4 == 0, n < 2^31.  Outside it the call returns MEVI_ERR_UNSUPPORTED and both queries 0.
+ *   mevi_rq_beam_encode_tile_docs: the documents one workgroup owns per step.  mevi_rq_beam_encode_workspace_bytes: pure
+ *   host arithmetic, positive inside the envelope and independent of n (one tile ticket for the persistent grid).
+ * Refusals, all before any launch and for n == 0 too, each naming its argument: the envelope (MEVI_ERR_UNSUPPORTED); null
+ *   or not 16-byte-aligned x / codebook, null labels, null workspace (MEVI_ERR_INVALID_ARG); last, a workspace below the
+ *   query (MEVI_ERR_WORKSPACE; the message carries the needed size).  Otherwise n == 0 returns MEVI_OK without a launch.
+ * No host synchronisation, no allocation: capturable in a HIP graph (one memset node and one kernel node). */
+size_t mevi_rq_beam_encode_workspace_bytes(int64_t n, int64_t dim, int64_t M, int64_t K, int64_t R, int pq);
+int64_t mevi_rq_beam_encode_tile_docs(int64_t dim, int64_t M, int64_t K, int64_t R, int pq);
+int mevi_rq_beam_encode_f32(const float *x, int64_t n, int64_t dim, const float *codebook, int64_t M, int64_t K,
+                            int64_t R, int pq, int32_t *labels, float *proba, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
 /* ------------------------------------------------------------------------
  * Centroid update of k-means / RQ codebook training (the offline index build the reference does with
  * scikit-learn, MEVI/pq.py:550-598; assignment = mevi_rq_encode_f32 with a one-level codebook):

@@ -148,6 +148,10 @@ _SIGNATURES = {
                                     c_int64, c_int, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
     "mevi_rq_neg_dist_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "mevi_gather_sub_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "mevi_rq_beam_encode_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "mevi_rq_beam_encode_tile_docs": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    "mevi_rq_beam_encode_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     "mevi_cluster_means_workspace_bytes": (ctypes.c_size_t, [c_int64, c_int64, c_int64]),
     "mevi_cluster_means_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),

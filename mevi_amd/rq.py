@@ -23,6 +23,7 @@ from . import hip
 
 
 _LAST_ENCODE = {}
+_BEAM_WORKSPACES = {}             # (device, stream, emb_size, M, K, R, pq) -> the fused beam encode's workspace
 
 
 def last_encode_stats():
@@ -409,9 +410,50 @@ class ProductQuantization:
         i32[bs, R, M] (and probabilities f32[bs, R])."""
         assert not do_sample and num_beams in (None, num_return_sequences)
         with hip.device_guard(self.device):          # stream_ptr() and the launches below refer to the codebook's GPU
-            return self._beam_search(doc_emb, num_return_sequences, return_proba)
+            if self.beam_search_is_fused(num_return_sequences):
+                return self._beam_search_fused(doc_emb, num_return_sequences, return_proba)
+            return self._beam_search_steps(doc_emb, num_return_sequences, return_proba)
 
-    def _beam_search(self, doc_emb, num_return_sequences, return_proba):
+    def beam_search_is_fused(self, num_return_sequences):
+        """True when `beam_search` takes mevi_rq_beam_encode_f32 (csrc/rq_beam.hip): not MEVI_RQ_BEAM=steps and the shape is
+        inside the kernel's envelope (R <= 16, ...); otherwise the per-level composition `_beam_search_steps` runs."""
+        import os
+
+        mode = os.environ.get("MEVI_RQ_BEAM", "fused")
+        assert mode in ("fused", "steps"), mode
+        return mode == "fused" and hip.lib().mevi_rq_beam_encode_tile_docs(
+            self.emb_size, self.subvector_num, self.subvector_cents, num_return_sequences, int(self.pq_type == "pq")) > 0
+
+    def _beam_workspace(self, n, R):
+        """The fused call's workspace, cached per (device, stream, shape): its size does not depend on n, and calls on one
+        stream run one after the other, so they can share the tile ticket it holds."""
+        pq = int(self.pq_type == "pq")
+        key = (self.device, hip.stream_ptr(), self.emb_size, self.subvector_num, self.subvector_cents, R, pq)
+        ws = _BEAM_WORKSPACES.get(key)
+        if ws is None:
+            nbytes = hip.lib().mevi_rq_beam_encode_workspace_bytes(n, self.emb_size, self.subvector_num, self.subvector_cents, R, pq)
+            ws = _BEAM_WORKSPACES[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _beam_search_fused(self, doc_emb, num_return_sequences, return_proba):
+        """All levels in one launch: reads x once, writes labels and probabilities only."""
+        R, M, K = num_return_sequences, self.subvector_num, self.subvector_cents
+        x = doc_emb.to(self.device, torch.float32).contiguous()
+        assert x.dim() == 2 and x.shape[1] == self.emb_size, (x.shape, self.emb_size)
+        bs = x.shape[0]
+        labels = torch.empty((bs, R, M), dtype=torch.int32, device=self.device)
+        proba = torch.empty((bs, R), dtype=torch.float32, device=self.device) if return_proba else None
+        if bs == 0:                                 # (an empty tensor has no address to hand over)
+            return (labels, proba) if return_proba else labels
+        ws = self._beam_workspace(bs, R)
+        st = hip.lib().mevi_rq_beam_encode_f32(hip.ptr(x), bs, self.emb_size, hip.ptr(self.codebook), M, K, R,
+                                               int(self.pq_type == "pq"), hip.ptr(labels), None if proba is None else hip.ptr(proba),
+                                               hip.ptr(ws), ws.numel(), hip.stream_ptr())
+        hip.check(st, "mevi_rq_beam_encode_f32")
+        return (labels, proba) if return_proba else labels
+
+    def _beam_search_steps(self, doc_emb, num_return_sequences, return_proba):
+        """The per-level composition (MEVI_RQ_BEAM=steps, and every shape outside the fused call's envelope)."""
         L = hip.lib()
         R, M, K, dim = num_return_sequences, self.subvector_num, self.subvector_cents, self.last_dim
         pq = self.pq_type == "pq"
@@ -456,10 +498,13 @@ class ProductQuantization:
 
     def get_topk_document_mapping(self, doc_embeddings, rank, nrank, num_return_sequences, batch_size=1 << 16):
         """Top-R code paths of this rank's contiguous slice of the corpus (pq.py:715-741: rows // nrank each, the last
-        rank takes the rest): i32 [rows, R, M] on the CPU."""
+        rank takes the rest): i32 [rows, R, M] on the CPU.  A CUDA tensor goes through the fused beam encode in one call
+        over the whole slice with one copy back; host arrays (numpy / memmap) are uploaded `batch_size` rows at a time."""
         n = doc_embeddings.shape[0]
         per = n // nrank
         start, end = per * rank, n if rank + 1 == nrank else per * (rank + 1)
+        if torch.is_tensor(doc_embeddings) and doc_embeddings.is_cuda and self.beam_search_is_fused(num_return_sequences):
+            return self.beam_search(doc_embeddings[start:end], num_return_sequences).cpu()   # one call, one copy back
         out = torch.empty((end - start, num_return_sequences, self.subvector_num), dtype=torch.int32)
         for s in range(start, end, batch_size):
             e = min(s + batch_size, end)

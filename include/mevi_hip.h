@@ -484,6 +484,44 @@ int mevi_attention_varlen_split_f16(const float *q, int64_t q_ts, const float *k
                                     void *out_img, int64_t img_np, int out_exp, int64_t img_ts, const int64_t *seq_off,
                                     int64_t nseq, int64_t max_len, int64_t heads, int64_t dh, const float *bias,
                                     int64_t bias_rows, int64_t bias_ld, int causal, float scale, void *stream);
+/* Which kernel a call of the attention entry points above takes: the value of the very function the launcher switches on
+ * (pure host arithmetic on the shape, the strides and the pointers' alignment; nothing is launched, no pointer is read).
+ * A negative value is a refusal: the MEVI_ERR_* status the call itself would return, with the message set.  The switches
+ * MEVI_ATTN_SHORT=chain, MEVI_ATTN_FEW_KEYS=direct and MEVI_ATTN_PASSAGE=f32 (read once per process) are honoured. */
+enum {
+  MEVI_ATTN_ROUTE_NONE = 0,             /* no rows: nothing is launched */
+  MEVI_ATTN_ROUTE_GENERIC = 1,          /* attention_kernel: one wave per (row, head, query) */
+  MEVI_ATTN_ROUTE_TILE = 2,             /* attention_tile_kernel: a whole sequence's Q, K, V in LDS */
+  MEVI_ATTN_ROUTE_GROUP = 3,            /* attention_group_kernel: the kv_div rows that share K|V */
+  MEVI_ATTN_ROUTE_FEW_KEYS = 4,         /* attention_few_keys_kernel: tq 1, <= 8 keys, per-lane row walk */
+  MEVI_ATTN_ROUTE_KEYS16 = 5,           /* attention_keys16_kernel: cached, 9..16 keys, heads not 64 wide */
+  MEVI_ATTN_ROUTE_VARLEN = 6,           /* attention_varlen_kernel */
+  MEVI_ATTN_ROUTE_VARLEN_SHORT64 = 7,   /* attention_varlen_short_kernel<64> */
+  MEVI_ATTN_ROUTE_MFMA = 8,             /* attention_mfma_kernel: 65..128 tokens on the f32 matrix cores */
+  MEVI_ATTN_ROUTE_H16 = 9,              /* attention_h16_kernel: the same in split f16, image output */
+  MEVI_ATTN_ROUTE_MFMA16_SELF = 10,     /* attention_mfma16_kernel mode 0: sequences of <= 32 tokens */
+  MEVI_ATTN_ROUTE_MFMA16_SHARED = 11,   /* attention_mfma16_kernel mode 1: <= 32 rows against <= 32 shared keys */
+  MEVI_ATTN_ROUTE_MFMA16_INDEXED = 12,  /* attention_mfma16_indexed_kernel: cached, 9..16 keys, 64-wide heads */
+  MEVI_ATTN_ROUTE_FEW_KEYS_STAGED64 = 64,   /* + tk (1..7): attention_few_keys_staged_kernel<tk, 64> */
+  MEVI_ATTN_ROUTE_FEW_KEYS_STAGED96 = 96    /* + tk (1..6): attention_few_keys_staged_kernel<tk, 96> */
+};
+/* The arguments of mevi_attention_f32 / _cached_f32 / _varlen_f32 without the stream, then the image of the *_split_f16
+ * form: out_img NULL asks about the f32 form; otherwise about the split form (`out` is ignored, o_bs / o_ts are img_bs /
+ * img_ts). */
+int mevi_attention_route(const float *q, int64_t q_bs, int64_t q_ts, const float *k, int64_t k_bs, int64_t k_ts,
+                         const float *v, int64_t v_bs, int64_t v_ts, const float *out, int64_t o_bs, int64_t o_ts, int64_t nb,
+                         int64_t tq, int64_t tk, int64_t heads, int64_t dh, int64_t kv_div, const float *bias,
+                         int64_t bias_rows, int64_t bias_ld, int64_t q_pos0, const int64_t *key_mask, int causal, float scale,
+                         const int64_t *kv_off, const void *out_img, int64_t img_np, int out_exp);
+int mevi_attention_varlen_route(const float *q, int64_t q_ts, const float *k, int64_t k_ts, const float *v, int64_t v_ts,
+                                const float *out, int64_t o_ts, const int64_t *seq_off, int64_t nseq, int64_t max_len,
+                                int64_t heads, int64_t dh, const float *bias, int64_t bias_rows, int64_t bias_ld, int causal,
+                                float scale, const void *out_img, int64_t img_np, int out_exp);
+int mevi_attention_cached_route(const float *q, int64_t q_bs, const float *k, int64_t k_bs, int64_t k_ts, const float *v,
+                                int64_t v_bs, int64_t v_ts, const float *out, int64_t o_bs, int64_t nb, int64_t tk,
+                                int64_t heads, int64_t dh, const int32_t *key_rows, const float *bias, int64_t bias_rows,
+                                int64_t bias_ld, int64_t q_pos0, int causal, float scale, const void *out_img, int64_t img_np,
+                                int out_exp);
 /* PAWA adaptive head on the valid columns only (modeling_t5.py:1607, 1677-1689):
  * out[row, c] = sum_d s[row, d] * (t[trow, c*dim + d] + e[c, d]),  t = adaptor_linear slice, e = lm_head rows;
  * trow = row when t_index is NULL, else t_index[row] (i64, device): the adaptor sees only the code prefix of a beam,

@@ -2072,13 +2072,38 @@ static bool short_mfma() {
   static const bool chain = [] { const char *e = getenv("MEVI_ATTN_SHORT"); return e && strcmp(e, "chain") == 0; }();
   return !chain;
 }
+
+// ---- which kernel a call takes ----------------------------------------------------------------------------------------------
+// One pure host function per launcher (attention_route, attention_varlen_route, attention_cached_route) holds every refusal
+// and every dispatch predicate and returns a MEVI_ATTN_ROUTE_* value (include/mevi_hip.h), or the negative MEVI_ERR_* status
+// of a refusal with the message set.  The launchers switch on that value and decide nothing themselves; the exported
+// mevi_attention*_route entry points return it without launching, so a test can name the kernel it ran.
+
 // passage-length self-attention: split-precision f16 matrix cores when the context goes out as a split image (= the caller runs
 // the split GEMMs); the f32-MFMA kernel otherwise (MEVI_GEMM=exact) or with MEVI_ATTN_PASSAGE=f32
-static int launch_passage(const AttnArgs &a, long long pairs, hipStream_t stream) {
-  MEVI_REQUIRE(a.q_ts >= 0 && a.k_ts >= 0 && a.v_ts >= 0 && a.q_ts < (1 << 24) && a.k_ts < (1 << 24) && a.v_ts < (1 << 24),
+static int passage_route(int64_t q_ts, int64_t k_ts, int64_t v_ts, bool image) {
+  MEVI_REQUIRE(q_ts >= 0 && k_ts >= 0 && v_ts >= 0 && q_ts < (1 << 24) && k_ts < (1 << 24) && v_ts < (1 << 24),
                MEVI_ERR_UNSUPPORTED, "attention: token strides of 2^24 floats or more");
   static const bool f32only = [] { const char *e = getenv("MEVI_ATTN_PASSAGE"); return e && strcmp(e, "f32") == 0; }();
-  if (a.oimg && !f32only) {
+  return image && !f32only ? MEVI_ATTN_ROUTE_H16 : MEVI_ATTN_ROUTE_MFMA;
+}
+static int mfma16_route(int route, int64_t q_bs, int64_t q_ts, int64_t k_ts, int64_t v_ts) {
+  // row offsets inside a group are formed in 32 bits (at most 32 rows of it)
+  MEVI_REQUIRE(k_ts < (1 << 24) && v_ts < (1 << 24) && q_ts < (1 << 24) && q_bs < (1 << 24) && k_ts >= 0 && v_ts >= 0 &&
+                   q_ts >= 0 && q_bs >= 0,
+               MEVI_ERR_UNSUPPORTED, "attention: row strides of 2^24 floats or more");
+  return route;
+}
+// 64- and 96-wide heads take the LDS-transposed form; MEVI_ATTN_FEW_KEYS=direct keeps the per-lane row walk (A/B, same bits)
+static int few_keys_route(int64_t dh, int64_t tk) {
+  static const bool direct = [] { const char *e = getenv("MEVI_ATTN_FEW_KEYS"); return e && strcmp(e, "direct") == 0; }();
+  // tk = 8 (and 7 at 96-wide heads): the staged form runs out of registers -- measured 4x slower than the direct one there
+  if ((dh != 64 && dh != 96) || direct || tk < 1 || tk > (dh == 64 ? 7 : 6)) return MEVI_ATTN_ROUTE_FEW_KEYS;
+  return (dh == 64 ? MEVI_ATTN_ROUTE_FEW_KEYS_STAGED64 : MEVI_ATTN_ROUTE_FEW_KEYS_STAGED96) + (int)tk;
+}
+
+static int launch_passage(const AttnArgs &a, int route, long long pairs, hipStream_t stream) {
+  if (route == MEVI_ATTN_ROUTE_H16) {
     MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_h16_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)AH_LDS));
     hipLaunchKernelGGL(attention_h16_kernel, dim3((unsigned)pairs), dim3(256), AH_LDS, stream, a);
@@ -2091,29 +2116,74 @@ static int launch_passage(const AttnArgs &a, long long pairs, hipStream_t stream
   return MEVI_OK;
 }
 static int launch_mfma16(const AttnArgs &a, int mode, long long pairs, hipStream_t stream) {
-  // row offsets inside a group are formed in 32 bits (at most 32 rows of it)
-  MEVI_REQUIRE(a.k_ts < (1 << 24) && a.v_ts < (1 << 24) && a.q_ts < (1 << 24) && a.q_bs < (1 << 24) && a.k_ts >= 0 && a.v_ts >= 0 &&
-                   a.q_ts >= 0 && a.q_bs >= 0,
-               MEVI_ERR_UNSUPPORTED, "attention: row strides of 2^24 floats or more");
   MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_mfma16_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)A16_LDS));
   hipLaunchKernelGGL(attention_mfma16_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), A16_LDS, stream, a, mode);
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;
 }
-// 64- and 96-wide heads take the LDS-transposed form; MEVI_ATTN_FEW_KEYS=direct keeps the per-lane row walk (A/B, same bits)
-typedef void (*few_keys_fn)(AttnArgs);
-static few_keys_fn few_keys_kernel(int64_t dh, int64_t tk) {
-  static const bool direct = [] { const char *e = getenv("MEVI_ATTN_FEW_KEYS"); return e && strcmp(e, "direct") == 0; }();
-  // tk = 8 (and 7 at 96-wide heads): the staged form runs out of registers -- measured 4x slower than the direct one there
-  if ((dh != 64 && dh != 96) || direct || tk < 1 || tk > (dh == 64 ? 7 : 6)) return attention_few_keys_kernel;
+// the eight-pairs-per-wave kernel of a few_keys_route value
+static int launch_few_keys(const AttnArgs &a, int route, long long pairs, hipStream_t stream) {
+  typedef void (*few_keys_fn)(AttnArgs);
 #define MEVI_FK(DH_) {attention_few_keys_staged_kernel<1, DH_>, attention_few_keys_staged_kernel<2, DH_>, attention_few_keys_staged_kernel<3, DH_>, \
                       attention_few_keys_staged_kernel<4, DH_>, attention_few_keys_staged_kernel<5, DH_>, attention_few_keys_staged_kernel<6, DH_>, \
                       attention_few_keys_staged_kernel<7, DH_>}
   static const few_keys_fn table64[7] = MEVI_FK(64), table96[7] = MEVI_FK(96);
 #undef MEVI_FK
-  const few_keys_fn *table = dh == 64 ? table64 : table96;
-  return table[tk - 1];
+  few_keys_fn fn = attention_few_keys_kernel;
+  if (route != MEVI_ATTN_ROUTE_FEW_KEYS) {
+    const bool w96 = route > MEVI_ATTN_ROUTE_FEW_KEYS_STAGED96;
+    const int tk = route - (w96 ? MEVI_ATTN_ROUTE_FEW_KEYS_STAGED96 : MEVI_ATTN_ROUTE_FEW_KEYS_STAGED64);
+    MEVI_REQUIRE(tk >= 1 && tk <= 7, MEVI_ERR_INVALID_ARG, "attention: no staged few-keys kernel for route %d", route);
+    fn = (w96 ? table96 : table64)[tk - 1];
+  }
+  hipLaunchKernelGGL(fn, dim3(blocks4((pairs + 7) / 8)), dim3(256), 0, stream, a);
+  MEVI_HIP_CHECK(hipGetLastError());
+  return MEVI_OK;
+}
+
+// LDS of attention_tile_kernel (Q, K, V tiles and a score row) and of attention_group_kernel (K, V, the group's q rows)
+static size_t attn_tile_lds(int64_t tk, int64_t dh) { return (size_t)tk * (3 * dh + 1) * sizeof(float); }
+static size_t attn_group_lds(int64_t tk, int64_t dh, int64_t kv_div) {
+  return ((size_t)tk * (2 * dh + 4) + (size_t)kv_div * dh) * sizeof(float);
+}
+
+static int attention_route(const float *q, int64_t q_bs, int64_t q_ts, const float *k, int64_t k_bs, int64_t k_ts,
+                           const float *v, int64_t v_bs, int64_t v_ts, const float *out, int64_t o_bs, int64_t o_ts,
+                           int64_t nb, int64_t tq, int64_t tk, int64_t heads, int64_t dh, int64_t kv_div, const float *bias,
+                           int64_t bias_rows, int64_t bias_ld, int64_t q_pos0, const int64_t *key_mask, int causal,
+                           float scale, const int64_t *kv_off, CtxImage ci) {
+  (void)bias_ld; (void)causal; (void)scale;
+  MEVI_REQUIRE(nb >= 0 && tq > 0 && tk > 0 && heads > 0 && dh > 0 && kv_div > 0, MEVI_ERR_INVALID_ARG,
+               "attention: bad shape");
+  MEVI_REQUIRE(tk <= 64 * ATT_KPL, MEVI_ERR_UNSUPPORTED, "attention: tk=%lld > %d keys not supported", (long long)tk,
+               64 * ATT_KPL);
+  MEVI_REQUIRE(dh <= 128, MEVI_ERR_UNSUPPORTED, "attention: head dim %lld > 128 not supported", (long long)dh);
+  MEVI_REQUIRE(dh % 4 == 0 && q_bs % 4 == 0 && q_ts % 4 == 0 && k_bs % 4 == 0 && k_ts % 4 == 0,
+               MEVI_ERR_INVALID_ARG, "attention: dh and q/k strides must be multiples of 4");
+  if (nb == 0) return MEVI_ATTN_ROUTE_NONE;
+  MEVI_REQUIRE(q && k && v && (out || ci.img), MEVI_ERR_INVALID_ARG, "attention: null pointer");
+  MEVI_REQUIRE(!bias || q_pos0 + tq <= bias_rows, MEVI_ERR_INVALID_ARG, "attention: bias table too small");
+  if (int st = ctx_image_check(ci, heads, dh, o_bs, o_ts)) return st;
+  // attention_mfma16_kernel moves rows as 16-byte pieces (q / k strides are checked above)
+  const bool mfma16_aligned = v_bs % 4 == 0 && v_ts % 4 == 0 && o_bs % 4 == 0 && o_ts % 4 == 0 &&
+                              (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0;
+  if (!kv_off && kv_div == 1 && tq == tk && tk > 64 && tk <= AM_S && dh == AM_D)   // passages: matrix cores
+    return passage_route(q_ts, k_ts, v_ts, ci.img != nullptr);
+  if (!kv_off && kv_div == 1 && tq == tk && tk > 1 && tk <= 32 && dh == AM_D && short_mfma() && mfma16_aligned)
+    return mfma16_route(MEVI_ATTN_ROUTE_MFMA16_SELF, q_bs, q_ts, k_ts, v_ts);   // query-length sequences
+  if (tq == 1 && tk <= 32 && kv_div <= 32 && nb % kv_div == 0 && dh == AM_D && short_mfma() && mfma16_aligned &&
+      (kv_off || key_mask || kv_div > 1 || tk > 8))   // a few rows against a few shared keys (cross-attention)
+    return mfma16_route(MEVI_ATTN_ROUTE_MFMA16_SHARED, q_bs, q_ts, k_ts, v_ts);
+  if (!kv_off && tq == 1 && tk <= 8) {  // a handful of cached keys: eight (row, head) pairs per wave
+    MEVI_REQUIRE(nb * heads < (1LL << 31) - 8, MEVI_ERR_UNSUPPORTED, "attention: too many (row, head) pairs");
+    return few_keys_route(dh, tk);
+  }
+  if (kv_div > 1 && tq == 1 && nb % kv_div == 0 && v_bs % 4 == 0 && v_ts % 4 == 0 && attn_group_lds(tk, dh, kv_div) <= 65536)
+    return MEVI_ATTN_ROUTE_GROUP;   // the beams of a query share K|V: stage them once per (query, head)
+  if (!kv_off && kv_div == 1 && tq == tk && tq >= 8 && attn_tile_lds(tk, dh) <= 160 * 1024)
+    return MEVI_ATTN_ROUTE_TILE;    // self-attention over a whole sequence
+  return MEVI_ATTN_ROUTE_GENERIC;
 }
 
 static int attention_launch(const float *q, int64_t q_bs, int64_t q_ts, const float *k, int64_t k_bs,
@@ -2122,20 +2192,13 @@ static int attention_launch(const float *q, int64_t q_bs, int64_t q_ts, const fl
                                   int64_t dh, int64_t kv_div, const float *bias, int64_t bias_rows,
                                   int64_t bias_ld, int64_t q_pos0, const int64_t *key_mask, int causal,
                                   float scale, const int64_t *kv_off, CtxImage ci, void *stream) {
-  MEVI_REQUIRE(nb >= 0 && tq > 0 && tk > 0 && heads > 0 && dh > 0 && kv_div > 0, MEVI_ERR_INVALID_ARG,
-               "attention: bad shape");
-  MEVI_REQUIRE(tk <= 64 * ATT_KPL, MEVI_ERR_UNSUPPORTED, "attention: tk=%lld > %d keys not supported", (long long)tk,
-               64 * ATT_KPL);
-  MEVI_REQUIRE(dh <= 128, MEVI_ERR_UNSUPPORTED, "attention: head dim %lld > 128 not supported", (long long)dh);
-  MEVI_REQUIRE(dh % 4 == 0 && q_bs % 4 == 0 && q_ts % 4 == 0 && k_bs % 4 == 0 && k_ts % 4 == 0,
-               MEVI_ERR_INVALID_ARG, "attention: dh and q/k strides must be multiples of 4");
-  if (nb == 0) return MEVI_OK;
-  MEVI_REQUIRE(q && k && v && (out || ci.img), MEVI_ERR_INVALID_ARG, "attention: null pointer");
-  MEVI_REQUIRE(!bias || q_pos0 + tq <= bias_rows, MEVI_ERR_INVALID_ARG, "attention: bias table too small");
+  const int route = attention_route(q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, out, o_bs, o_ts, nb, tq, tk, heads, dh, kv_div,
+                                    bias, bias_rows, bias_ld, q_pos0, key_mask, causal, scale, kv_off, ci);
+  if (route < 0) return route;                            // refused: the status, message set
+  if (route == MEVI_ATTN_ROUTE_NONE) return MEVI_OK;      // no rows
   AttnArgs a;
   a.q = q; a.k = k; a.v = v; a.out = out;
   a.oimg = ci.img; a.onp = ci.np; a.oexp = ci.exp;
-  if (int st = ctx_image_check(ci, heads, dh, o_bs, o_ts)) return st;
   a.q_bs = q_bs; a.q_ts = q_ts; a.k_bs = k_bs; a.k_ts = k_ts; a.v_bs = v_bs; a.v_ts = v_ts; a.o_bs = o_bs; a.o_ts = o_ts;
   a.nb = (int)nb; a.tq = (int)tq; a.tk = (int)tk; a.H = (int)heads; a.dh = (int)dh; a.kv_div = (int)kv_div;
   a.bias = bias; a.bias_rows = (int)bias_rows; a.bias_ld = (int)bias_ld; a.q_pos0 = (int)q_pos0;
@@ -2143,57 +2206,73 @@ static int attention_launch(const float *q, int64_t q_bs, int64_t q_ts, const fl
   a.seq_off = nullptr;
   a.kv_off = reinterpret_cast<const long long *>(kv_off);
   a.key_rows = nullptr;
-  const size_t tile_lds = (size_t)tk * (3 * dh + 1) * sizeof(float);
-  // attention_mfma16_kernel moves rows as 16-byte pieces (q / k strides are checked above)
-  const bool mfma16_aligned = v_bs % 4 == 0 && v_ts % 4 == 0 && o_bs % 4 == 0 && o_ts % 4 == 0 &&
-                              (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0;
-  if (!kv_off && kv_div == 1 && tq == tk && tk > 64 && tk <= AM_S && dh == AM_D) {  // passages: matrix cores
-    return launch_passage(a, (long long)nb * heads, (hipStream_t)stream);
-  } else if (!kv_off && kv_div == 1 && tq == tk && tk > 1 && tk <= 32 && dh == AM_D && short_mfma() && mfma16_aligned) {  // query-length sequences
-    return launch_mfma16(a, 0, (long long)nb * heads, (hipStream_t)stream);
-  } else if (tq == 1 && tk <= 32 && kv_div <= 32 && nb % kv_div == 0 && dh == AM_D && short_mfma() && mfma16_aligned &&
-             (kv_off || key_mask || kv_div > 1 || tk > 8)) {   // a few rows against a few shared keys (cross-attention)
-    return launch_mfma16(a, 1, (nb / kv_div) * heads, (hipStream_t)stream);
-  } else if (!kv_off && tq == 1 && tk <= 8) {  // a handful of cached keys: eight (row, head) pairs per wave
-    MEVI_REQUIRE(nb * heads < (1LL << 31) - 8, MEVI_ERR_UNSUPPORTED, "attention: too many (row, head) pairs");
-    hipLaunchKernelGGL(few_keys_kernel(dh, tk), dim3(blocks4((nb * heads + 7) / 8)), dim3(256), 0, (hipStream_t)stream, a);
-  } else if (kv_div > 1 && tq == 1 && nb % kv_div == 0 && v_bs % 4 == 0 && v_ts % 4 == 0 &&
-             ((size_t)tk * (2 * dh + 4) + (size_t)kv_div * dh) * sizeof(float) <= 65536) {
-    // the beams of a query share K|V: stage them once per (query, head)
-    hipLaunchKernelGGL(attention_group_kernel, dim3((unsigned)((nb / kv_div) * heads)), dim3(256),
-                       ((size_t)tk * (2 * dh + 4) + (size_t)kv_div * dh) * sizeof(float), (hipStream_t)stream, a);
-  } else if (!kv_off && kv_div == 1 && tq == tk && tq >= 8 && tile_lds <= 160 * 1024) {  // self-attention over a whole sequence
-    if (tile_lds > 65536)  // dynamic LDS beyond 64 KiB must be opted into (128 passage tokens x 64: 97 KiB)
-      MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_tile_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
-    hipLaunchKernelGGL(attention_tile_kernel, dim3((unsigned)(nb * heads)), dim3(256), tile_lds, (hipStream_t)stream, a);
-  } else {
-    hipLaunchKernelGGL(attention_kernel, dim3(blocks4(nb * heads * tq)), dim3(256), 0, (hipStream_t)stream, a);
+  switch (route) {
+    case MEVI_ATTN_ROUTE_MFMA:
+    case MEVI_ATTN_ROUTE_H16:
+      return launch_passage(a, route, (long long)nb * heads, (hipStream_t)stream);
+    case MEVI_ATTN_ROUTE_MFMA16_SELF:
+      return launch_mfma16(a, 0, (long long)nb * heads, (hipStream_t)stream);
+    case MEVI_ATTN_ROUTE_MFMA16_SHARED:
+      return launch_mfma16(a, 1, (nb / kv_div) * heads, (hipStream_t)stream);
+    case MEVI_ATTN_ROUTE_GROUP:
+      hipLaunchKernelGGL(attention_group_kernel, dim3((unsigned)((nb / kv_div) * heads)), dim3(256),
+                         attn_group_lds(tk, dh, kv_div), (hipStream_t)stream, a);
+      break;
+    case MEVI_ATTN_ROUTE_TILE: {
+      const size_t tile_lds = attn_tile_lds(tk, dh);
+      if (tile_lds > 65536)  // dynamic LDS beyond 64 KiB must be opted into (128 passage tokens x 64: 97 KiB)
+        MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_tile_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+      hipLaunchKernelGGL(attention_tile_kernel, dim3((unsigned)(nb * heads)), dim3(256), tile_lds, (hipStream_t)stream, a);
+      break;
+    }
+    case MEVI_ATTN_ROUTE_GENERIC:
+      hipLaunchKernelGGL(attention_kernel, dim3(blocks4(nb * heads * tq)), dim3(256), 0, (hipStream_t)stream, a);
+      break;
+    default:   // MEVI_ATTN_ROUTE_FEW_KEYS and the staged forms
+      return launch_few_keys(a, route, (long long)nb * heads, (hipStream_t)stream);
   }
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;
+}
+
+static int attention_varlen_route(const float *q, int64_t q_ts, const float *k, int64_t k_ts, const float *v, int64_t v_ts,
+                                  const float *out, int64_t o_ts, const int64_t *seq_off, int64_t nseq, int64_t max_len,
+                                  int64_t heads, int64_t dh, const float *bias, int64_t bias_rows, int64_t bias_ld, int causal,
+                                  float scale, CtxImage ci) {
+  (void)causal; (void)scale;
+  MEVI_REQUIRE(nseq >= 0 && max_len > 0 && heads > 0 && dh > 0, MEVI_ERR_INVALID_ARG, "attention_varlen: bad shape");
+  MEVI_REQUIRE(max_len <= 64 * ATT_KPL, MEVI_ERR_UNSUPPORTED, "attention_varlen: %lld > %d keys not supported",
+               (long long)max_len, 64 * ATT_KPL);
+  MEVI_REQUIRE(dh <= 128 && dh % 4 == 0 && q_ts % 4 == 0 && k_ts % 4 == 0 && v_ts % 4 == 0, MEVI_ERR_INVALID_ARG,
+               "attention_varlen: dh (<= 128) and the row strides must be multiples of 4");
+  MEVI_REQUIRE(attn_tile_lds(max_len, dh) <= 160 * 1024, MEVI_ERR_UNSUPPORTED, "attention_varlen: %lld keys x %lld do not fit LDS",
+               (long long)max_len, (long long)dh);
+  if (nseq == 0) return MEVI_ATTN_ROUTE_NONE;
+  MEVI_REQUIRE(q && k && v && (out || ci.img) && seq_off, MEVI_ERR_INVALID_ARG, "attention_varlen: null pointer");
+  MEVI_REQUIRE(!bias || (max_len <= bias_rows && max_len <= bias_ld), MEVI_ERR_INVALID_ARG,
+               "attention_varlen: bias table too small");
+  if (int st = ctx_image_check(ci, heads, dh, 0, o_ts)) return st;
+  if (max_len > 64 && max_len <= AM_S && dh == AM_D)   // passage-length sequences: matrix cores
+    return passage_route(q_ts, k_ts, v_ts, ci.img != nullptr);
+  if (max_len <= 32 && dh == AM_D && short_mfma() && o_ts % 4 == 0 &&
+      (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0)
+    return mfma16_route(MEVI_ATTN_ROUTE_MFMA16_SELF, 0, q_ts, k_ts, v_ts);
+  if (max_len <= 64 && dh == 64) return MEVI_ATTN_ROUTE_VARLEN_SHORT64;   // t5-base / bert-base heads, query-length sequences
+  return MEVI_ATTN_ROUTE_VARLEN;
 }
 
 static int attention_varlen_launch(const float *q, int64_t q_ts, const float *k, int64_t k_ts, const float *v,
                                          int64_t v_ts, float *out, int64_t o_ts, const int64_t *seq_off, int64_t nseq,
                                          int64_t max_len, int64_t heads, int64_t dh, const float *bias,
                                          int64_t bias_rows, int64_t bias_ld, int causal, float scale, CtxImage ci, void *stream) {
-  MEVI_REQUIRE(nseq >= 0 && max_len > 0 && heads > 0 && dh > 0, MEVI_ERR_INVALID_ARG, "attention_varlen: bad shape");
-  MEVI_REQUIRE(max_len <= 64 * ATT_KPL, MEVI_ERR_UNSUPPORTED, "attention_varlen: %lld > %d keys not supported",
-               (long long)max_len, 64 * ATT_KPL);
-  MEVI_REQUIRE(dh <= 128 && dh % 4 == 0 && q_ts % 4 == 0 && k_ts % 4 == 0 && v_ts % 4 == 0, MEVI_ERR_INVALID_ARG,
-               "attention_varlen: dh (<= 128) and the row strides must be multiples of 4");
-  const size_t per_wave = (size_t)max_len * (3 * dh + 1) * sizeof(float);
-  MEVI_REQUIRE(per_wave <= 160 * 1024, MEVI_ERR_UNSUPPORTED, "attention_varlen: %lld keys x %lld do not fit LDS",
-               (long long)max_len, (long long)dh);
-  if (nseq == 0) return MEVI_OK;
-  MEVI_REQUIRE(q && k && v && (out || ci.img) && seq_off, MEVI_ERR_INVALID_ARG, "attention_varlen: null pointer");
-  MEVI_REQUIRE(!bias || (max_len <= bias_rows && max_len <= bias_ld), MEVI_ERR_INVALID_ARG,
-               "attention_varlen: bias table too small");
+  const int route = attention_varlen_route(q, q_ts, k, k_ts, v, v_ts, out, o_ts, seq_off, nseq, max_len, heads, dh, bias, bias_rows,
+                                           bias_ld, causal, scale, ci);
+  if (route < 0) return route;                            // refused: the status, message set
+  if (route == MEVI_ATTN_ROUTE_NONE) return MEVI_OK;      // no sequences
   AttnArgs a;
   a.q = q; a.k = k; a.v = v; a.out = out;
   a.oimg = ci.img; a.onp = ci.np; a.oexp = ci.exp;
-  if (int st = ctx_image_check(ci, heads, dh, 0, o_ts)) return st;
   a.q_bs = a.k_bs = a.v_bs = a.o_bs = 0;
   a.q_ts = q_ts; a.k_ts = k_ts; a.v_ts = v_ts; a.o_ts = o_ts;
   a.nb = (int)nseq; a.tq = a.tk = (int)max_len; a.H = (int)heads; a.dh = (int)dh; a.kv_div = 1;
@@ -2203,20 +2282,17 @@ static int attention_varlen_launch(const float *q, int64_t q_ts, const float *k,
   a.kv_off = nullptr;
   a.key_rows = nullptr;
   const long long pairs = (long long)nseq * heads;
-  if (max_len > 64 && max_len <= AM_S && dh == AM_D) {   // passage-length sequences: matrix cores
-    a.q_pos0 = 0;
-    return launch_passage(a, pairs, (hipStream_t)stream);
-  }
-  if (max_len <= 32 && dh == AM_D && short_mfma() && o_ts % 4 == 0 &&
-      (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0)
-    return launch_mfma16(a, 0, pairs, (hipStream_t)stream);
-  if (max_len <= 64 && dh == 64) {   // t5-base / bert-base heads, query-length sequences
+  if (route == MEVI_ATTN_ROUTE_MFMA || route == MEVI_ATTN_ROUTE_H16) return launch_passage(a, route, pairs, (hipStream_t)stream);
+  if (route == MEVI_ATTN_ROUTE_MFMA16_SELF) return launch_mfma16(a, 0, pairs, (hipStream_t)stream);
+  if (route == MEVI_ATTN_ROUTE_VARLEN_SHORT64) {
     hipLaunchKernelGGL(attention_varlen_short_kernel<64>, dim3((unsigned)((pairs + 3) / 4)), dim3(256),
                        (size_t)4 * max_len * 2 * 64 * sizeof(float), (hipStream_t)stream, a, (int)max_len);
     MEVI_HIP_CHECK(hipGetLastError());
     return MEVI_OK;
   }
+  // MEVI_ATTN_ROUTE_VARLEN
   // as many waves per workgroup as keep two workgroups' LDS regions on a CU (one when the region is large)
+  const size_t per_wave = attn_tile_lds(max_len, dh);
   int waves = (int)(80 * 1024 / per_wave);
   waves = waves < 1 ? 1 : waves > 4 ? 4 : waves;
   const size_t lds = per_wave * waves;
@@ -2229,45 +2305,57 @@ static int attention_varlen_launch(const float *q, int64_t q_ts, const float *k,
   return MEVI_OK;
 }
 
-static int attention_cached_launch(const float *q, int64_t q_bs, const float *k, int64_t k_bs, int64_t k_ts, const float *v,
-                                         int64_t v_bs, int64_t v_ts, float *out, int64_t o_bs, int64_t nb, int64_t tk,
-                                         int64_t heads, int64_t dh, const int32_t *key_rows, const float *bias,
-                                         int64_t bias_rows, int64_t bias_ld, int64_t q_pos0, int causal, float scale,
-                                         CtxImage ci, void *stream) {
+static int attention_cached_route(const float *q, int64_t q_bs, const float *k, int64_t k_bs, int64_t k_ts, const float *v,
+                                  int64_t v_bs, int64_t v_ts, const float *out, int64_t o_bs, int64_t nb, int64_t tk, int64_t heads,
+                                  int64_t dh, const int32_t *key_rows, const float *bias, int64_t bias_rows, int64_t bias_ld,
+                                  int64_t q_pos0, int causal, float scale, CtxImage ci) {
+  (void)causal; (void)scale;
   MEVI_REQUIRE(nb >= 0 && tk > 0 && tk <= 16 && heads > 0 && dh > 0 && dh <= 128 && dh % 4 == 0, MEVI_ERR_UNSUPPORTED,
                "attention_cached: 1..16 cached positions, head width a multiple of 4 up to 128 (got tk %lld, dh %lld)",
                (long long)tk, (long long)dh);
   MEVI_REQUIRE(q_bs % 4 == 0 && k_bs % 4 == 0 && k_ts % 4 == 0 && v_bs % 4 == 0 && v_ts % 4 == 0, MEVI_ERR_INVALID_ARG,
                "attention_cached: strides must be multiples of 4");
-  if (nb == 0) return MEVI_OK;
+  if (nb == 0) return MEVI_ATTN_ROUTE_NONE;
   MEVI_REQUIRE(q && k && v && (out || ci.img) && key_rows, MEVI_ERR_INVALID_ARG, "attention_cached: null pointer");
   MEVI_REQUIRE(!bias || (q_pos0 < bias_rows && tk <= bias_ld), MEVI_ERR_INVALID_ARG, "attention_cached: bias table too small");
+  if (int st = ctx_image_check(ci, heads, dh, o_bs, 0)) return st;
+  MEVI_REQUIRE(nb * heads < (1LL << 31) - 8, MEVI_ERR_UNSUPPORTED, "attention_cached: too many (row, head) pairs");
+  if (tk > 8) {
+    // 9 .. 16 keys: the kernel attention_launch picks for (tq 1, this tk, kv_div 1) on a re-ordered copy, fed through key_rows
+    const bool mfma16_aligned = o_bs % 4 == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0;
+    return dh == AM_D && short_mfma() && mfma16_aligned ? MEVI_ATTN_ROUTE_MFMA16_INDEXED : MEVI_ATTN_ROUTE_KEYS16;
+  }
+  return few_keys_route(dh, tk);
+}
+
+static int attention_cached_launch(const float *q, int64_t q_bs, const float *k, int64_t k_bs, int64_t k_ts, const float *v,
+                                         int64_t v_bs, int64_t v_ts, float *out, int64_t o_bs, int64_t nb, int64_t tk,
+                                         int64_t heads, int64_t dh, const int32_t *key_rows, const float *bias,
+                                         int64_t bias_rows, int64_t bias_ld, int64_t q_pos0, int causal, float scale,
+                                         CtxImage ci, void *stream) {
+  const int route = attention_cached_route(q, q_bs, k, k_bs, k_ts, v, v_bs, v_ts, out, o_bs, nb, tk, heads, dh, key_rows, bias,
+                                           bias_rows, bias_ld, q_pos0, causal, scale, ci);
+  if (route < 0) return route;                            // refused: the status, message set
+  if (route == MEVI_ATTN_ROUTE_NONE) return MEVI_OK;      // no rows
   AttnArgs a;
   a.q = q; a.k = k; a.v = v; a.out = out;
   a.oimg = ci.img; a.onp = ci.np; a.oexp = ci.exp;
-  if (int st = ctx_image_check(ci, heads, dh, o_bs, 0)) return st;
   a.q_bs = q_bs; a.q_ts = 0; a.k_bs = k_bs; a.k_ts = k_ts; a.v_bs = v_bs; a.v_ts = v_ts; a.o_bs = o_bs; a.o_ts = 0;
   a.nb = (int)nb; a.tq = 1; a.tk = (int)tk; a.H = (int)heads; a.dh = (int)dh; a.kv_div = 1;
   a.bias = bias; a.bias_rows = (int)bias_rows; a.bias_ld = (int)bias_ld; a.q_pos0 = (int)q_pos0;
   a.key_mask = nullptr; a.causal = causal; a.scale = scale;
   a.seq_off = nullptr; a.kv_off = nullptr;
   a.key_rows = key_rows;
-  MEVI_REQUIRE(nb * heads < (1LL << 31) - 8, MEVI_ERR_UNSUPPORTED, "attention_cached: too many (row, head) pairs");
-  if (tk > 8) {
-    // 9 .. 16 keys: the kernel attention_launch picks for (tq 1, this tk, kv_div 1) on a re-ordered copy, fed through key_rows
-    const bool mfma16_aligned = o_bs % 4 == 0 && (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0;
-    if (dh == AM_D && short_mfma() && mfma16_aligned) {
-      MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_mfma16_indexed_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)A16_LDS));
-      hipLaunchKernelGGL(attention_mfma16_indexed_kernel, dim3((unsigned)((nb * heads + 3) / 4)), dim3(256), A16_LDS,
-                         (hipStream_t)stream, a);
-    } else {
-      hipLaunchKernelGGL(attention_keys16_kernel, dim3(blocks4((nb * heads + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-    }
-    MEVI_HIP_CHECK(hipGetLastError());
-    return MEVI_OK;
+  if (route == MEVI_ATTN_ROUTE_MFMA16_INDEXED) {
+    MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(attention_mfma16_indexed_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)A16_LDS));
+    hipLaunchKernelGGL(attention_mfma16_indexed_kernel, dim3((unsigned)((nb * heads + 3) / 4)), dim3(256), A16_LDS,
+                       (hipStream_t)stream, a);
+  } else if (route == MEVI_ATTN_ROUTE_KEYS16) {
+    hipLaunchKernelGGL(attention_keys16_kernel, dim3(blocks4((nb * heads + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  } else {   // MEVI_ATTN_ROUTE_FEW_KEYS and the staged forms
+    return launch_few_keys(a, route, (long long)nb * heads, (hipStream_t)stream);
   }
-  hipLaunchKernelGGL(few_keys_kernel(dh, tk), dim3(blocks4((nb * heads + 7) / 8)), dim3(256), 0, (hipStream_t)stream, a);
   MEVI_HIP_CHECK(hipGetLastError());
   return MEVI_OK;
 }
@@ -2335,6 +2423,42 @@ extern "C" int mevi_attention_cached_split_f16(const float *q, int64_t q_bs, con
   return attention_cached_launch(q, q_bs, k, k_bs, k_ts, v, v_bs, v_ts, nullptr, img_bs, nb, tk, heads, dh, key_rows, bias,
                                  bias_rows, bias_ld, q_pos0, causal, scale,
                                  CtxImage{reinterpret_cast<_Float16 *>(out_img), (int)img_np, out_exp}, stream);
+}
+
+// Which kernel the calls above would launch (MEVI_ATTN_ROUTE_*, or the negative status of the refusal): the launchers' own
+// decision functions, nothing launched.  out_img null: the *_f32 form; else the *_split_f16 form (`out` unused, o_bs / o_ts
+// = img_bs / img_ts).
+static CtxImage route_image(const float *&out, const void *out_img, int64_t img_np, int out_exp) {
+  if (!out_img) return CtxImage{nullptr, 0, 0};
+  out = nullptr;
+  return CtxImage{reinterpret_cast<_Float16 *>(const_cast<void *>(out_img)), (int)img_np, out_exp};
+}
+extern "C" int mevi_attention_route(const float *q, int64_t q_bs, int64_t q_ts, const float *k, int64_t k_bs, int64_t k_ts,
+                                    const float *v, int64_t v_bs, int64_t v_ts, const float *out, int64_t o_bs, int64_t o_ts,
+                                    int64_t nb, int64_t tq, int64_t tk, int64_t heads, int64_t dh, int64_t kv_div,
+                                    const float *bias, int64_t bias_rows, int64_t bias_ld, int64_t q_pos0,
+                                    const int64_t *key_mask, int causal, float scale, const int64_t *kv_off,
+                                    const void *out_img, int64_t img_np, int out_exp) {
+  const CtxImage ci = route_image(out, out_img, img_np, out_exp);
+  return attention_route(q, q_bs, q_ts, k, k_bs, k_ts, v, v_bs, v_ts, out, o_bs, o_ts, nb, tq, tk, heads, dh, kv_div, bias,
+                         bias_rows, bias_ld, q_pos0, key_mask, causal, scale, kv_off, ci);
+}
+extern "C" int mevi_attention_varlen_route(const float *q, int64_t q_ts, const float *k, int64_t k_ts, const float *v, int64_t v_ts,
+                                           const float *out, int64_t o_ts, const int64_t *seq_off, int64_t nseq, int64_t max_len,
+                                           int64_t heads, int64_t dh, const float *bias, int64_t bias_rows, int64_t bias_ld,
+                                           int causal, float scale, const void *out_img, int64_t img_np, int out_exp) {
+  const CtxImage ci = route_image(out, out_img, img_np, out_exp);
+  return attention_varlen_route(q, q_ts, k, k_ts, v, v_ts, out, o_ts, seq_off, nseq, max_len, heads, dh, bias, bias_rows, bias_ld,
+                                causal, scale, ci);
+}
+extern "C" int mevi_attention_cached_route(const float *q, int64_t q_bs, const float *k, int64_t k_bs, int64_t k_ts, const float *v,
+                                           int64_t v_bs, int64_t v_ts, const float *out, int64_t o_bs, int64_t nb, int64_t tk,
+                                           int64_t heads, int64_t dh, const int32_t *key_rows, const float *bias,
+                                           int64_t bias_rows, int64_t bias_ld, int64_t q_pos0, int causal, float scale,
+                                           const void *out_img, int64_t img_np, int out_exp) {
+  const CtxImage ci = route_image(out, out_img, img_np, out_exp);
+  return attention_cached_route(q, q_bs, k, k_bs, k_ts, v, v_bs, v_ts, out, o_bs, nb, tk, heads, dh, key_rows, bias, bias_rows,
+                                bias_ld, q_pos0, causal, scale, ci);
 }
 
 extern "C" int mevi_adaptive_logits_rows_f32(const float *s, int64_t lds_, float alpha, const float *te, int64_t ldt,

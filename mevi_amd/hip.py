@@ -119,6 +119,16 @@ _SIGNATURES = {
     "mevi_attention_varlen_split_f16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                                 c_int, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                                 c_int64, c_int64, c_int, c_float, c_void_p]),
+    "mevi_attention_route": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                     c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                     c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_float, c_void_p,
+                                     c_void_p, c_int64, c_int]),
+    "mevi_attention_varlen_route": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                            c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                            c_int, c_float, c_void_p, c_int64, c_int]),
+    "mevi_attention_cached_route": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
+                                            c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                            c_int64, c_int, c_float, c_void_p, c_int64, c_int]),
     "mevi_adaptive_logits_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                          c_int64, c_void_p, c_void_p]),
     "mevi_adaptive_logits_rows_f32": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_int64, c_void_p, c_int64, c_int64,
@@ -183,6 +193,22 @@ _FINE_AGG_SIGNATURES = {
                                        c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_float, c_float,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
+
+
+# MEVI_ATTN_ROUTE_* of include/mevi_hip.h: what mevi_attention*_route return (negative: the status of a refusal)
+ATTN_ROUTES = {"NONE": 0, "GENERIC": 1, "TILE": 2, "GROUP": 3, "FEW_KEYS": 4, "KEYS16": 5, "VARLEN": 6, "VARLEN_SHORT64": 7,
+               "MFMA": 8, "H16": 9, "MFMA16_SELF": 10, "MFMA16_SHARED": 11, "MFMA16_INDEXED": 12,
+               "FEW_KEYS_STAGED64": 64, "FEW_KEYS_STAGED96": 96}     # the staged forms: + tk (1..7 / 1..6)
+
+
+def attn_route_name(route):
+    """'TILE', 'FEW_KEYS_STAGED64+3', ... for a route value; 'REFUSED(-2)' for a refusal."""
+    if route < 0:
+        return f"REFUSED({route})"
+    for base in ("FEW_KEYS_STAGED96", "FEW_KEYS_STAGED64"):
+        if ATTN_ROUTES[base] < route <= ATTN_ROUTES[base] + 7:
+            return f"{base}+{route - ATTN_ROUTES[base]}"
+    return next(k for k, v in ATTN_ROUTES.items() if v == route)
 
 
 def exported_symbols(header="mevi_hip.h"):

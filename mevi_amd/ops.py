@@ -532,19 +532,44 @@ def attention(q, k, v, heads, out=None, kv_div=1, bias=None, q_pos0=0, key_mask=
     kv_off (i64 [nb/kv_div + 1], device), PACKED k/v [rows, H*dh]: kv batch c owns rows kv_off[c] .. kv_off[c+1]-1, all
     real, kv_longest = the longest of them.  split_bound (ctx_bound): return the context as the SplitRows image
     [nb * tq, H*dh] of the o-projection instead of f32 [nb, tq, H*dh]."""
-    assert q.dim() == 3 and q.stride(2) == 1 and q.is_cuda and q.dtype == torch.float32
+    # `mask`: the key mask as the kernel reads it (a converted copy unless it already is int64, contiguous and on the device);
+    # it must stay alive in this frame until the launch is queued -- `tail` only carries its address
+    nb, tq, hd, head, tail, mask = _attention_args(q, k, v, heads, kv_div, bias, q_pos0, key_mask, causal, scale, kv_off,
+                                                   kv_longest, True)
+    if split_bound is not None:
+        assert out is None
+        ctx, kp, e = _ctx_image(nb * tq, hd, split_bound, q.device)
+        st = hip.lib().mevi_attention_split_f16(*head, hip.ptr(ctx.img), kp, e, tq * 2 * kp, 2 * kp, *tail, hip.stream_ptr())
+        hip.check(st, "mevi_attention_split_f16")
+        del mask
+        return ctx
+    if out is None:
+        out = torch.empty((nb, tq, hd), dtype=torch.float32, device=q.device)
+    st = hip.lib().mevi_attention_f32(*head, hip.ptr(out), out.stride(0), out.stride(1), *tail, hip.stream_ptr())
+    hip.check(st, "mevi_attention_f32")
+    del mask
+    return out
+
+
+def _attention_args(q, k, v, heads, kv_div, bias, q_pos0, key_mask, causal, scale, kv_off, kv_longest, on_gpu):
+    """(nb, tq, H*dh, head, tail, mask) of an `attention` call: mevi_attention_f32 / _split_f16 / _route take `head`, then where
+    the context goes, then `tail` (then the stream, or for the route the image).  `tail` holds ADDRESSES: `mask` is the tensor
+    behind the key-mask address (None without a mask) and the caller keeps it until its launch is queued.  on_gpu: the operands
+    must be device tensors (attention_route only does arithmetic on their addresses and takes host tensors too)."""
+    dev = (lambda t: t.is_cuda) if on_gpu else (lambda t: True)
+    assert q.dim() == 3 and q.stride(2) == 1 and dev(q) and q.dtype == torch.float32
     nb, tq, hd = q.shape
     dh = hd // heads
     if kv_off is None:
         for t in (k, v):
-            assert t.dim() == 3 and t.stride(2) == 1 and t.is_cuda and t.dtype == torch.float32
+            assert t.dim() == 3 and t.stride(2) == 1 and dev(t) and t.dtype == torch.float32
         tk = k.shape[1]
         assert k.shape[0] * kv_div == nb and v.shape[:2] == k.shape[:2]
         kst, vst = (k.stride(0), k.stride(1)), (v.stride(0), v.stride(1))
     else:
         for t in (k, v):
-            assert t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == torch.float32
-        assert kv_off.dtype == torch.int64 and kv_off.is_cuda and kv_off.numel() * kv_div == nb + kv_div and key_mask is None
+            assert t.dim() == 2 and t.stride(1) == 1 and dev(t) and t.dtype == torch.float32
+        assert kv_off.dtype == torch.int64 and dev(kv_off) and kv_off.numel() * kv_div == nb + kv_div and key_mask is None
         tk = int(kv_longest)
         kst, vst = (0, k.stride(0)), (0, v.stride(0))
     brows = bld = 0
@@ -554,27 +579,36 @@ def attention(q, k, v, heads, out=None, kv_div=1, bias=None, q_pos0=0, key_mask=
     if key_mask is not None:
         key_mask = key_mask.to(device=q.device, dtype=torch.int64).contiguous()
         assert key_mask.shape == (nb // kv_div, tk)
-    if split_bound is not None:
-        assert out is None
-        ctx, kp, e = _ctx_image(nb * tq, hd, split_bound, q.device)
-        st = hip.lib().mevi_attention_split_f16(
-            hip.ptr(q), q.stride(0), q.stride(1), hip.ptr(k), kst[0], kst[1], hip.ptr(v), vst[0], vst[1],
-            hip.ptr(ctx.img), kp, e, tq * 2 * kp, 2 * kp, nb, tq, tk, heads, dh, kv_div,
-            hip.ptr(bias) if bias is not None else None, brows, bld, q_pos0,
+    head = (hip.ptr(q), q.stride(0), q.stride(1), hip.ptr(k), kst[0], kst[1], hip.ptr(v), vst[0], vst[1])
+    tail = (nb, tq, tk, heads, dh, kv_div, hip.ptr(bias) if bias is not None else None, brows, bld, q_pos0,
             hip.ptr(key_mask) if key_mask is not None else None, 1 if causal else 0, scale,
-            hip.ptr(kv_off) if kv_off is not None else None, hip.stream_ptr())
-        hip.check(st, "mevi_attention_split_f16")
-        return ctx
-    if out is None:
-        out = torch.empty((nb, tq, hd), dtype=torch.float32, device=q.device)
-    st = hip.lib().mevi_attention_f32(
-        hip.ptr(q), q.stride(0), q.stride(1), hip.ptr(k), kst[0], kst[1], hip.ptr(v), vst[0], vst[1],
-        hip.ptr(out), out.stride(0), out.stride(1), nb, tq, tk, heads, dh, kv_div,
-        hip.ptr(bias) if bias is not None else None, brows, bld, q_pos0,
-        hip.ptr(key_mask) if key_mask is not None else None, 1 if causal else 0, scale,
-        hip.ptr(kv_off) if kv_off is not None else None, hip.stream_ptr())
-    hip.check(st, "mevi_attention_f32")
-    return out
+            hip.ptr(kv_off) if kv_off is not None else None)
+    return nb, tq, hd, head, tail, key_mask
+
+
+_FRESH = 256      # stands for the address of an output `attention*` would allocate itself (the allocator's alignment); never read
+
+
+def _route_image(hd, out, split_bound):
+    """(image address, np, exponent) the *_route entry points take: zeros for an f32 output, else what `_ctx_image` would
+    give `attention*` for split_bound -- without allocating it."""
+    if split_bound is None:
+        return None, 0, 0
+    assert out is None
+    return _FRESH, split_kp(hd), _pow2_exp(split_bound * 1.001)
+
+
+def attention_route(q, k, v, heads, out=None, kv_div=1, bias=None, q_pos0=0, key_mask=None, causal=False, scale=1.0,
+                    kv_off=None, kv_longest=0, split_bound=None):
+    """The kernel `attention` takes for these arguments (a MEVI_ATTN_ROUTE_* value of include/mevi_hip.h: hip.ATTN_ROUTES names
+    them; negative: the status of the refusal) -- the launcher's own decision, nothing launched, host tensors allowed."""
+    nb, tq, hd, head, tail, _ = _attention_args(q, k, v, heads, kv_div, bias, q_pos0, key_mask, causal, scale, kv_off, kv_longest,
+                                                False)
+    img, kp, e = _route_image(hd, out, split_bound)
+    if img is not None:
+        return hip.lib().mevi_attention_route(*head, None, tq * 2 * kp, 2 * kp, *tail, img, kp, e)
+    where = (_FRESH, tq * hd, hd) if out is None else (hip.ptr(out), out.stride(0), out.stride(1))
+    return hip.lib().mevi_attention_route(*head, *where, *tail, None, 0, 0)
 
 
 @hip.on_device
@@ -582,64 +616,92 @@ def attention_cached(q, k, v, key_rows, heads, bias=None, q_pos0=0, causal=True,
     """One decode step over ancestor-indexed caches: q [n, H*dh]; k / v [rows, T, H*dh] views of the caches (any row / token
     strides); key_rows i32 [n, tk] (tk <= 16): position j of row b is cache row key_rows[b, j].  Same bits as `attention` on the
     caches physically re-ordered by the beams' parents (generation_utils.py:927-934)."""
-    assert q.dim() == 2 and q.stride(1) == 1 and q.is_cuda and q.dtype == torch.float32
+    n, hd, head, tail = _attention_cached_args(q, k, v, key_rows, heads, bias, q_pos0, causal, scale, True)
+    if split_bound is not None:      # the context as the o-projection's SplitRows image (see attention)
+        assert out is None
+        ctx, kp, e = _ctx_image(n, hd, split_bound, q.device)
+        st = hip.lib().mevi_attention_cached_split_f16(*head, hip.ptr(ctx.img), kp, e, 2 * kp, *tail, hip.stream_ptr())
+        hip.check(st, "mevi_attention_cached_split_f16")
+        return ctx
+    if out is None:
+        out = torch.empty((n, hd), dtype=torch.float32, device=q.device)
+    st = hip.lib().mevi_attention_cached_f32(*head, hip.ptr(out), out.stride(0), *tail, hip.stream_ptr())
+    hip.check(st, "mevi_attention_cached_f32")
+    return out
+
+
+def _attention_cached_args(q, k, v, key_rows, heads, bias, q_pos0, causal, scale, on_gpu):
+    """(n, H*dh, head, tail) of an `attention_cached` call (see _attention_args)."""
+    dev = (lambda t: t.is_cuda) if on_gpu else (lambda t: True)
+    assert q.dim() == 2 and q.stride(1) == 1 and dev(q) and q.dtype == torch.float32
     for t in (k, v):
-        assert t.dim() == 3 and t.stride(2) == 1 and t.is_cuda and t.dtype == torch.float32
+        assert t.dim() == 3 and t.stride(2) == 1 and dev(t) and t.dtype == torch.float32
     n, hd = q.shape
-    assert key_rows.dtype == torch.int32 and key_rows.is_cuda and key_rows.is_contiguous() and key_rows.shape[0] == n
+    assert key_rows.dtype == torch.int32 and dev(key_rows) and key_rows.is_contiguous() and key_rows.shape[0] == n
     tk = key_rows.shape[1]
     brows = bld = 0
     if bias is not None:
         assert bias.dim() == 3 and bias.is_contiguous() and bias.shape[0] == heads
         brows, bld = bias.shape[1], bias.shape[2]
-    if split_bound is not None:      # the context as the o-projection's SplitRows image (see attention)
-        assert out is None
-        ctx, kp, e = _ctx_image(n, hd, split_bound, q.device)
-        st = hip.lib().mevi_attention_cached_split_f16(
-            hip.ptr(q), q.stride(0), hip.ptr(k), k.stride(0), k.stride(1), hip.ptr(v), v.stride(0), v.stride(1),
-            hip.ptr(ctx.img), kp, e, 2 * kp, n, tk, heads, hd // heads, hip.ptr(key_rows),
-            hip.ptr(bias) if bias is not None else None, brows, bld, q_pos0, 1 if causal else 0, scale, hip.stream_ptr())
-        hip.check(st, "mevi_attention_cached_split_f16")
-        return ctx
-    if out is None:
-        out = torch.empty((n, hd), dtype=torch.float32, device=q.device)
-    st = hip.lib().mevi_attention_cached_f32(
-        hip.ptr(q), q.stride(0), hip.ptr(k), k.stride(0), k.stride(1), hip.ptr(v), v.stride(0), v.stride(1), hip.ptr(out),
-        out.stride(0), n, tk, heads, hd // heads, hip.ptr(key_rows), hip.ptr(bias) if bias is not None else None, brows, bld,
-        q_pos0, 1 if causal else 0, scale, hip.stream_ptr())
-    hip.check(st, "mevi_attention_cached_f32")
-    return out
+    head = (hip.ptr(q), q.stride(0), hip.ptr(k), k.stride(0), k.stride(1), hip.ptr(v), v.stride(0), v.stride(1))
+    tail = (n, tk, heads, hd // heads, hip.ptr(key_rows), hip.ptr(bias) if bias is not None else None, brows, bld, q_pos0,
+            1 if causal else 0, scale)
+    return n, hd, head, tail
+
+
+def attention_cached_route(q, k, v, key_rows, heads, bias=None, q_pos0=0, causal=True, scale=1.0, out=None, split_bound=None):
+    """The kernel `attention_cached` takes for these arguments (see attention_route)."""
+    n, hd, head, tail = _attention_cached_args(q, k, v, key_rows, heads, bias, q_pos0, causal, scale, False)
+    img, kp, e = _route_image(hd, out, split_bound)
+    if img is not None:
+        return hip.lib().mevi_attention_cached_route(*head, None, 2 * kp, *tail, img, kp, e)
+    where = (_FRESH, hd) if out is None else (hip.ptr(out), out.stride(0))
+    return hip.lib().mevi_attention_cached_route(*head, *where, *tail, None, 0, 0)
 
 
 @hip.on_device
 def attention_varlen(q, k, v, seq_off, max_len, heads, bias=None, causal=False, scale=1.0, out=None, split_bound=None):
     """Self-attention over packed sequences: q / k / v [T, H*dh] row-strided views, sequence b = rows
     seq_off[b] .. seq_off[b+1]-1 (i64 [nseq+1] on the device), max_len = longest sequence (<= 256)."""
-    for t in (q, k, v):
-        assert t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == torch.float32
-    T, hd = q.shape
-    assert seq_off.dtype == torch.int64 and seq_off.is_cuda and seq_off.is_contiguous()
-    brows = bld = 0
-    if bias is not None:
-        assert bias.dim() == 3 and bias.is_contiguous() and bias.shape[0] == heads
-        brows, bld = bias.shape[1], bias.shape[2]
+    T, hd, head, tail = _attention_varlen_args(q, k, v, seq_off, max_len, heads, bias, causal, scale, True)
     if split_bound is not None:      # the context as the o-projection's SplitRows image (see attention)
         assert out is None
         ctx, kp, e = _ctx_image(T, hd, split_bound, q.device)
-        st = hip.lib().mevi_attention_varlen_split_f16(
-            hip.ptr(q), q.stride(0), hip.ptr(k), k.stride(0), hip.ptr(v), v.stride(0), hip.ptr(ctx.img), kp, e, 2 * kp,
-            hip.ptr(seq_off), seq_off.numel() - 1, int(max_len), heads, hd // heads,
-            hip.ptr(bias) if bias is not None else None, brows, bld, 1 if causal else 0, scale, hip.stream_ptr())
+        st = hip.lib().mevi_attention_varlen_split_f16(*head, hip.ptr(ctx.img), kp, e, 2 * kp, *tail, hip.stream_ptr())
         hip.check(st, "mevi_attention_varlen_split_f16")
         return ctx
     if out is None:
         out = torch.empty((T, hd), dtype=torch.float32, device=q.device)
-    st = hip.lib().mevi_attention_varlen_f32(
-        hip.ptr(q), q.stride(0), hip.ptr(k), k.stride(0), hip.ptr(v), v.stride(0), hip.ptr(out), out.stride(0),
-        hip.ptr(seq_off), seq_off.numel() - 1, int(max_len), heads, hd // heads,
-        hip.ptr(bias) if bias is not None else None, brows, bld, 1 if causal else 0, scale, hip.stream_ptr())
+    st = hip.lib().mevi_attention_varlen_f32(*head, hip.ptr(out), out.stride(0), *tail, hip.stream_ptr())
     hip.check(st, "mevi_attention_varlen_f32")
     return out
+
+
+def _attention_varlen_args(q, k, v, seq_off, max_len, heads, bias, causal, scale, on_gpu):
+    """(T, H*dh, head, tail) of an `attention_varlen` call (see _attention_args)."""
+    dev = (lambda t: t.is_cuda) if on_gpu else (lambda t: True)
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.stride(1) == 1 and dev(t) and t.dtype == torch.float32
+    T, hd = q.shape
+    assert seq_off.dtype == torch.int64 and dev(seq_off) and seq_off.is_contiguous()
+    brows = bld = 0
+    if bias is not None:
+        assert bias.dim() == 3 and bias.is_contiguous() and bias.shape[0] == heads
+        brows, bld = bias.shape[1], bias.shape[2]
+    head = (hip.ptr(q), q.stride(0), hip.ptr(k), k.stride(0), hip.ptr(v), v.stride(0))
+    tail = (hip.ptr(seq_off), seq_off.numel() - 1, int(max_len), heads, hd // heads,
+            hip.ptr(bias) if bias is not None else None, brows, bld, 1 if causal else 0, scale)
+    return T, hd, head, tail
+
+
+def attention_varlen_route(q, k, v, seq_off, max_len, heads, bias=None, causal=False, scale=1.0, out=None, split_bound=None):
+    """The kernel `attention_varlen` takes for these arguments (see attention_route)."""
+    T, hd, head, tail = _attention_varlen_args(q, k, v, seq_off, max_len, heads, bias, causal, scale, False)
+    img, kp, e = _route_image(hd, out, split_bound)
+    if img is not None:
+        return hip.lib().mevi_attention_varlen_route(*head, None, 2 * kp, *tail, img, kp, e)
+    where = (_FRESH, hd) if out is None else (hip.ptr(out), out.stride(0))
+    return hip.lib().mevi_attention_varlen_route(*head, *where, *tail, None, 0, 0)
 
 
 @hip.on_device

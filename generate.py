@@ -118,7 +118,13 @@ def gen_query_embedding(rank, query_file, model_path, ckpt_path, tokenizer_path,
 def gen_doc_embedding(rank, document_dir, model_path, ckpt_path, output_path, batch_size, dim, gpus, doc_length=128,
                       encoder=None):
     """all_document_tokens.bin / all_document_masks.bin (i64 [N, doc_length]) -> f32 [N, dim] at `output_path`
-    (MEVI/generate.py:116-187: per-rank part files `<output>_<rank>.bin`, merged by rank 0)."""
+    (MEVI/generate.py:116-187: per-rank part files `<output>_<rank>.bin`, merged by rank 0).
+
+    doc_length (--doc_length) is the width the passages were tokenised to.  Up to 256 tokens the tower runs the kernels it
+    always ran; longer passages (NQ / Wikipedia passages of 256-384 tokens, document-level MARCO; up to 2048 tokens, for
+    the BERT towers up to their 512 positions) run the block-streaming attention (ops.attention_long*).  A device pass
+    holds DEVICE_PASS_TOKENS padded tokens whatever the length; measured at t5-base shapes, ragged lengths: 0.75 of the
+    128-token rate in real tokens per second at 384 tokens, 0.65 at 512 (tools/bench_long_passages.py)."""
     import torch
     import torch.distributed as dist
 

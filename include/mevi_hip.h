@@ -522,6 +522,10 @@ int mevi_attention_cached_route(const float *q, int64_t q_bs, const float *k, in
                                 int64_t heads, int64_t dh, const int32_t *key_rows, const float *bias, int64_t bias_rows,
                                 int64_t bias_ld, int64_t q_pos0, int causal, float scale, const void *out_img, int64_t img_np,
                                 int out_exp);
+/* More than 256 keys (up to MEVI_ATTN_LONG_MAX_KEYS): the `_long` forms of the f32 and varlen calls and their route
+ * functions, declared and documented in mevi_hip_attn_long.h with their two route values (13 and 14).  The calls above keep
+ * their envelope. */
+#include "mevi_hip_attn_long.h"
 /* PAWA adaptive head on the valid columns only (modeling_t5.py:1607, 1677-1689):
  * out[row, c] = sum_d s[row, d] * (t[trow, c*dim + d] + e[c, d]),  t = adaptor_linear slice, e = lm_head rows;
  * trow = row when t_index is NULL, else t_index[row] (i64, device): the adaptor sees only the code prefix of a beam,

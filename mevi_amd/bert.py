@@ -6,7 +6,7 @@ attention with the 1/sqrt(d) scale and the key mask)."""
 import torch
 
 from . import ops
-from .t5 import DEVICE_PASS_TOKENS, packed_offsets, varlen_ok
+from .t5 import DEVICE_PASS_TOKENS, LONG_KEYS, packed_offsets, varlen_ok
 
 
 def _dev(w, name, device):
@@ -52,11 +52,16 @@ class BertEncoder:
         self.dh = self.d // num_heads
 
     def forward(self, input_ids, attention_mask, pack=None):
-        """input_ids / attention_mask i64[B, S] (S <= 256, token types all 0) -> last hidden state f32[B, S, d].
+        """input_ids / attention_mask i64[B, S] (S <= the position table's rows, 512 for the BERT family; token types all
+        0) -> last hidden state f32[B, S, d].  Attention calls of more than 256 keys (a packed batch whose longest
+        sequence is longer, a padded layout with S > 256) run on the block-streaming kernels (ops.attention_long*, f32
+        context); every other decision is the one it always was.
 
         pack (default: self.pack): per-token operators run on the real tokens only, the padded layout is used for
         attention alone (as mevi_amd.t5.EncoderStack.forward); padded positions of the result are 0."""
         B, S = input_ids.shape
+        if S > self.pos.shape[0]:
+            raise ValueError(f"BertEncoder: {S} positions per sequence, the position table has {self.pos.shape[0]} rows")
         d = self.d
         pack = self.pack if pack is None else pack
         idx = None
@@ -72,7 +77,8 @@ class BertEncoder:
         x = ops.gather_rows(self.word, tok)
         x = ops.add_layernorm(x, pos, self.emb_ln[0], self.emb_ln[1], eps=self.eps, cvec=self.type0)
         seq_off, longest = packed_offsets(attention_mask) if idx is not None else (None, 0)
-        varlen = seq_off is not None and varlen_ok(longest, self.dh)    # right-padded: attend on the packed rows
+        # right-padded: attend on the packed rows
+        varlen = seq_off is not None and (varlen_ok(longest, self.dh) or longest > LONG_KEYS)
         qkv = None if idx is None or varlen else torch.zeros((B * S, 3 * d), dtype=torch.float32, device=x.device)
         for L in self.layers:
             xg = ops.gemm_input(x)
@@ -80,14 +86,22 @@ class BertEncoder:
                 q3 = ops.linear(xg, L["wqkv"], bias=L["bqkv"]).view(B, S, 3 * d)
             elif varlen:
                 q2 = ops.linear(xg, L["wqkv"], bias=L["bqkv"])
-                ctx = ops.attention_varlen(q2[:, :d], q2[:, d:2 * d], q2[:, 2 * d:], seq_off, longest, self.H, scale=scale,
-                                           split_bound=L["vb"])
+                if longest > LONG_KEYS:
+                    ctx = ops.attention_long_varlen(q2[:, :d], q2[:, d:2 * d], q2[:, 2 * d:], seq_off, longest, self.H, scale=scale)
+                else:
+                    ctx = ops.attention_varlen(q2[:, :d], q2[:, d:2 * d], q2[:, 2 * d:], seq_off, longest, self.H, scale=scale,
+                                               split_bound=L["vb"])
             else:
                 q3 = ops.scatter_rows(ops.linear(xg, L["wqkv"], bias=L["bqkv"]), idx, qkv).view(B, S, 3 * d)
-            if not varlen:
+            if not varlen and S > LONG_KEYS:
+                vb = None
+                ctx = ops.attention_long(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], self.H, key_mask=attention_mask,
+                                         scale=scale)
+            elif not varlen:
                 vb = L["vb"] if idx is None else None      # the scattered form gathers its context rows: f32
                 ctx = ops.attention(q3[:, :, :d], q3[:, :, d:2 * d], q3[:, :, 2 * d:], self.H, key_mask=attention_mask,
                                     scale=scale, split_bound=vb)
+            if not varlen:
                 if vb is None:
                     ctx = ctx.view(B * S, d)
                 if idx is not None:

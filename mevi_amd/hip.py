@@ -195,6 +195,19 @@ _FINE_AGG_SIGNATURES = {
 }
 
 
+# include/mevi_hip_attn_long.h (included by mevi_hip.h): attention over up to ATTN_LONG_MAX_KEYS keys
+_ATTN_LONG_SIGNATURES = {
+    "mevi_attention_long_f32": _SIGNATURES["mevi_attention_f32"],
+    "mevi_attention_long_varlen_f32": _SIGNATURES["mevi_attention_varlen_f32"],
+    "mevi_attention_long_route": (c_int, _SIGNATURES["mevi_attention_f32"][1][:-1]),            # the call without the stream
+    "mevi_attention_long_varlen_route": (c_int, _SIGNATURES["mevi_attention_varlen_f32"][1][:-1]),
+}
+ATTN_LONG_MAX_KEYS = 2048     # MEVI_ATTN_LONG_MAX_KEYS
+# MEVI_ATTN_ROUTE_* of that header: what mevi_attention_long*_route return besides NONE.  A table of their own: ATTN_ROUTES is
+# the enum of mevi_hip.h, name for name, and every name of it has its cases in tests/attn_cases.py
+ATTN_LONG_ROUTES = {"LONG_MFMA": 13, "LONG_ROWS": 14}
+
+
 # MEVI_ATTN_ROUTE_* of include/mevi_hip.h: what mevi_attention*_route return (negative: the status of a refusal)
 ATTN_ROUTES = {"NONE": 0, "GENERIC": 1, "TILE": 2, "GROUP": 3, "FEW_KEYS": 4, "KEYS16": 5, "VARLEN": 6, "VARLEN_SHORT64": 7,
                "MFMA": 8, "H16": 9, "MFMA16_SELF": 10, "MFMA16_SHARED": 11, "MFMA16_INDEXED": 12,
@@ -202,18 +215,20 @@ ATTN_ROUTES = {"NONE": 0, "GENERIC": 1, "TILE": 2, "GROUP": 3, "FEW_KEYS": 4, "K
 
 
 def attn_route_name(route):
-    """'TILE', 'FEW_KEYS_STAGED64+3', ... for a route value; 'REFUSED(-2)' for a refusal."""
+    """'TILE', 'FEW_KEYS_STAGED64+3', 'LONG_MFMA', ... for a route value; 'REFUSED(-2)' for a refusal."""
     if route < 0:
         return f"REFUSED({route})"
     for base in ("FEW_KEYS_STAGED96", "FEW_KEYS_STAGED64"):
         if ATTN_ROUTES[base] < route <= ATTN_ROUTES[base] + 7:
             return f"{base}+{route - ATTN_ROUTES[base]}"
-    return next(k for k, v in ATTN_ROUTES.items() if v == route)
+    return next(k for k, v in {**ATTN_ROUTES, **ATTN_LONG_ROUTES}.items() if v == route)
 
 
 def exported_symbols(header="mevi_hip.h"):
-    """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h, which it includes)."""
-    return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES}[header])
+    """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h,
+    which it includes)."""
+    return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES,
+                   "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES}[header])
 
 
 def lib():
@@ -224,7 +239,7 @@ def lib():
                 f"{LIB} not found: build it with `python -m mevi_amd.build` "
                 "(or __graft_entry__.build()); mevi_amd has no CPU fallback")
         L = ctypes.CDLL(LIB)
-        for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -59,7 +59,10 @@ def embed_documents(encoder, tokens, masks, output_path, rank=0, nrank=1, barrie
 def load_passage_tokens(args, tokenizer=None):
     """--document_path: either the prefix of `<prefix>_tokens.bin` / `<prefix>_masks.bin` (i64 [N, co_doc_length],
     prepare_passage_tokenized.py) or a `.tsv` of `id \\t title \\t content` tokenised here (main_models.py:1465-1491,
-    3117-3131: 'Title: .. Text: ..' for T5-ANCE, `title [SEP] content` for the BERT towers)."""
+    3117-3131: 'Title: .. Text: ..' for T5-ANCE, `title [SEP] content` for the BERT towers).
+
+    --co_doc_length may exceed 256: the towers then attend through the block-streaming kernels (ops.attention_long*, up
+    to 2048 tokens; a BERT tower raises past its position table, 512 rows for the BERT family)."""
     length = getattr(args, "co_doc_length", None) or 128
     if not args.document_path.endswith(".tsv"):
         tok = np.memmap(args.document_path + "_tokens.bin", dtype=np.int64, mode="r").reshape(-1, length)

@@ -662,7 +662,7 @@ def attention_cached_route(q, k, v, key_rows, heads, bias=None, q_pos0=0, causal
 @hip.on_device
 def attention_varlen(q, k, v, seq_off, max_len, heads, bias=None, causal=False, scale=1.0, out=None, split_bound=None):
     """Self-attention over packed sequences: q / k / v [T, H*dh] row-strided views, sequence b = rows
-    seq_off[b] .. seq_off[b+1]-1 (i64 [nseq+1] on the device), max_len = longest sequence (<= 256)."""
+    seq_off[b] .. seq_off[b+1]-1 (i64 [nseq+1] on the device), max_len = longest sequence (<= 256; attention_long_varlen beyond)."""
     T, hd, head, tail = _attention_varlen_args(q, k, v, seq_off, max_len, heads, bias, causal, scale, True)
     if split_bound is not None:      # the context as the o-projection's SplitRows image (see attention)
         assert out is None
@@ -702,6 +702,53 @@ def attention_varlen_route(q, k, v, seq_off, max_len, heads, bias=None, causal=F
         return hip.lib().mevi_attention_varlen_route(*head, None, 2 * kp, *tail, img, kp, e)
     where = (_FRESH, hd) if out is None else (hip.ptr(out), out.stride(0))
     return hip.lib().mevi_attention_varlen_route(*head, *where, *tail, None, 0, 0)
+
+
+# ---- more than 256 keys (include/mevi_hip_attn_long.h): the keys walked in blocks, up to hip.ATTN_LONG_MAX_KEYS ----------------
+
+@hip.on_device
+def attention_long(q, k, v, heads, out=None, kv_div=1, bias=None, q_pos0=0, key_mask=None, causal=False, scale=1.0,
+                   kv_off=None, kv_longest=0):
+    """`attention` for 1 .. hip.ATTN_LONG_MAX_KEYS keys (same operands, same conventions): self-attention on 64-wide heads
+    runs on the f32 matrix cores in blocks of 128 keys, everything else one wave per query.  The context is always f32
+    [nb, tq, H*dh] (there is no split-image form)."""
+    nb, tq, hd, head, tail, mask = _attention_args(q, k, v, heads, kv_div, bias, q_pos0, key_mask, causal, scale, kv_off,
+                                                   kv_longest, True)
+    if out is None:
+        out = torch.empty((nb, tq, hd), dtype=torch.float32, device=q.device)
+    st = hip.lib().mevi_attention_long_f32(*head, hip.ptr(out), out.stride(0), out.stride(1), *tail, hip.stream_ptr())
+    hip.check(st, "mevi_attention_long_f32")
+    del mask       # alive until the launch is queued (see attention)
+    return out
+
+
+def attention_long_route(q, k, v, heads, out=None, kv_div=1, bias=None, q_pos0=0, key_mask=None, causal=False, scale=1.0,
+                         kv_off=None, kv_longest=0):
+    """The kernel `attention_long` takes for these arguments (hip.ATTN_LONG_ROUTES, 0 for no rows, negative: the status of
+    the refusal) -- the launcher's own decision, nothing launched, host tensors allowed."""
+    nb, tq, hd, head, tail, _ = _attention_args(q, k, v, heads, kv_div, bias, q_pos0, key_mask, causal, scale, kv_off, kv_longest,
+                                                False)
+    where = (_FRESH, tq * hd, hd) if out is None else (hip.ptr(out), out.stride(0), out.stride(1))
+    return hip.lib().mevi_attention_long_route(*head, *where, *tail)
+
+
+@hip.on_device
+def attention_long_varlen(q, k, v, seq_off, max_len, heads, bias=None, causal=False, scale=1.0, out=None):
+    """`attention_varlen` for sequences of up to hip.ATTN_LONG_MAX_KEYS tokens; the context is f32 [T, H*dh].  Same bits as
+    `attention_long` on the padded layout with the key mask, on the real rows."""
+    T, hd, head, tail = _attention_varlen_args(q, k, v, seq_off, max_len, heads, bias, causal, scale, True)
+    if out is None:
+        out = torch.empty((T, hd), dtype=torch.float32, device=q.device)
+    st = hip.lib().mevi_attention_long_varlen_f32(*head, hip.ptr(out), out.stride(0), *tail, hip.stream_ptr())
+    hip.check(st, "mevi_attention_long_varlen_f32")
+    return out
+
+
+def attention_long_varlen_route(q, k, v, seq_off, max_len, heads, bias=None, causal=False, scale=1.0, out=None):
+    """The kernel `attention_long_varlen` takes for these arguments (see attention_long_route)."""
+    T, hd, head, tail = _attention_varlen_args(q, k, v, seq_off, max_len, heads, bias, causal, scale, False)
+    where = (_FRESH, hd) if out is None else (hip.ptr(out), out.stride(0))
+    return hip.lib().mevi_attention_long_varlen_route(*head, *where, *tail)
 
 
 @hip.on_device

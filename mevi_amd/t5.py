@@ -118,7 +118,10 @@ class EncoderStack(_PreNormBlocks):
         return self._bias[S]
 
     def forward(self, embeddings, input_ids, attention_mask, pack=None):
-        """input_ids/attention_mask i64[B, S] (S <= 256) -> last hidden state f32[B, S, d_model].
+        """input_ids/attention_mask i64[B, S] (S <= ops.hip.ATTN_LONG_MAX_KEYS) -> last hidden state f32[B, S, d_model].
+        Up to LONG_KEYS = 256 keys per attention call every decision below is the one it always was; where a call would
+        carry more (a packed batch whose longest sequence is longer, a padded layout with S > 256) the block-streaming
+        kernels run instead (ops.attention_long*), with an f32 context into `o`.
 
         pack (default: self.pack): run every per-token operator (norms, the five linear layers of a block) on the REAL
         tokens of the batch only and use the padded [B, S] layout just for attention.  The reference pads every
@@ -140,19 +143,29 @@ class EncoderStack(_PreNormBlocks):
             x = self._start(ops.gather_rows(embeddings, input_ids.reshape(-1)))
             for L in self.layers:
                 qkv = self._nl(x, L, "ln0", "wqkv").view(B, S, 3 * d.inner)
-                ctx = ops.attention(qkv[:, :, :d.inner], qkv[:, :, d.inner:2 * d.inner], qkv[:, :, 2 * d.inner:],
-                                    d.num_heads, bias=bias, key_mask=attention_mask, split_bound=L["vb"])
-                x = self._rl(ctx if L["vb"] is not None else ctx.view(B * S, d.inner), L, "wo", x)
+                if S > LONG_KEYS:
+                    ctx = ops.attention_long(qkv[:, :, :d.inner], qkv[:, :, d.inner:2 * d.inner], qkv[:, :, 2 * d.inner:],
+                                             d.num_heads, bias=bias, key_mask=attention_mask).view(B * S, d.inner)
+                else:
+                    ctx = ops.attention(qkv[:, :, :d.inner], qkv[:, :, d.inner:2 * d.inner], qkv[:, :, 2 * d.inner:],
+                                        d.num_heads, bias=bias, key_mask=attention_mask, split_bound=L["vb"])
+                    if L["vb"] is None:
+                        ctx = ctx.view(B * S, d.inner)
+                x = self._rl(ctx, L, "wo", x)
                 x = self._rl(self._nl(x, L, "ln1", "wi", relu=True, for_gemm=True), L, "wo2", x)
             return self._final(x).view(B, S, d.d_model)
         x = self._start(ops.gather_rows(embeddings, input_ids.reshape(-1)[idx]))            # [T, d_model], T real tokens
         seq_off, longest = packed_offsets(attention_mask)
-        if seq_off is not None and varlen_ok(longest, d.d_kv):
+        if seq_off is not None and (varlen_ok(longest, d.d_kv) or longest > LONG_KEYS):
             # right-padded sequences (what the tokenizers produce): attention runs on the packed rows too
             for L in self.layers:
                 qkv = self._nl(x, L, "ln0", "wqkv")
-                ctx = ops.attention_varlen(qkv[:, :d.inner], qkv[:, d.inner:2 * d.inner], qkv[:, 2 * d.inner:], seq_off,
-                                           longest, d.num_heads, bias=bias, split_bound=L["vb"])
+                if longest > LONG_KEYS:
+                    ctx = ops.attention_long_varlen(qkv[:, :d.inner], qkv[:, d.inner:2 * d.inner], qkv[:, 2 * d.inner:], seq_off,
+                                                    longest, d.num_heads, bias=bias)
+                else:
+                    ctx = ops.attention_varlen(qkv[:, :d.inner], qkv[:, d.inner:2 * d.inner], qkv[:, 2 * d.inner:], seq_off,
+                                               longest, d.num_heads, bias=bias, split_bound=L["vb"])
                 x = self._rl(ctx, L, "wo", x)
                 x = self._rl(self._nl(x, L, "ln1", "wi", relu=True, for_gemm=True), L, "wo2", x)
         else:
@@ -160,8 +173,9 @@ class EncoderStack(_PreNormBlocks):
             for L in self.layers:
                 ops.scatter_rows(self._nl(x, L, "ln0", "wqkv"), idx, qkv)
                 q3 = qkv.view(B, S, 3 * d.inner)
-                ctx = ops.attention(q3[:, :, :d.inner], q3[:, :, d.inner:2 * d.inner], q3[:, :, 2 * d.inner:],
-                                    d.num_heads, bias=bias, key_mask=attention_mask)
+                attend = ops.attention_long if S > LONG_KEYS else ops.attention
+                ctx = attend(q3[:, :, :d.inner], q3[:, :, d.inner:2 * d.inner], q3[:, :, 2 * d.inner:],
+                             d.num_heads, bias=bias, key_mask=attention_mask)
                 x = self._rl(ops.gather_rows(ctx.view(B * S, d.inner), idx), L, "wo", x)
                 x = self._rl(self._nl(x, L, "ln1", "wi", relu=True, for_gemm=True), L, "wo2", x)
         out = torch.zeros((B * S, d.d_model), dtype=torch.float32, device=x.device)
@@ -174,6 +188,9 @@ class EncoderStack(_PreNormBlocks):
 # padded layout
 VARLEN_MAX_KEYS = 64
 VARLEN_MFMA_KEYS, VARLEN_MFMA_DH = 128, 64
+# the most keys ops.attention / ops.attention_varlen take in one call; a call with more goes to ops.attention_long*
+# (sequences of 129 .. 256 tokens keep the kernels they always had)
+LONG_KEYS = 256
 
 
 def varlen_ok(longest, dh):
@@ -312,7 +329,7 @@ class DecoderStack(_PreNormBlocks):
         positions are projected; for right-padded masks the K|V rows stay PACKED (the attention kernels read a
         sequence's real keys through its row offsets), otherwise they are scattered into a zeroed [B, S, 2*inner]
         buffer.  pack=False projects every position and keeps the mask: fixed shapes, no host synchronisation (the
-        graph-replay path of small batches)."""
+        graph-replay path of small batches).  Encoder states of more than 256 positions are fine in every form."""
         B, S, dm = enc.shape
         flat = enc.reshape(B * S, dm)
         idx = None
@@ -326,7 +343,7 @@ class DecoderStack(_PreNormBlocks):
             return CrossKV([kv[:, :, l * w2:(l + 1) * w2] for l in range(nl)], enc_mask)
         real = ops.gather_rows(flat, idx)
         seq_off, longest = packed_offsets(enc_mask)
-        if seq_off is not None and 0 < longest <= 256:
+        if seq_off is not None and 0 < longest:       # any length: `step` reads more than LONG_KEYS keys through attention_long
             kv = ops.linear(real, self.xkv_all)
             return CrossKV([kv[:, l * w2:(l + 1) * w2] for l in range(nl)], None, seq_off, longest)
         real = ops.gemm_input(real)        # one operand image for all layers
@@ -383,13 +400,20 @@ class DecoderStack(_PreNormBlocks):
             if ctx is not None:
                 x = self._rl(ctx, L, "wo", x)
             q = self._nl(x, L, "ln1", "xq")
-            if xkv.kv_off is None:
+            xlong = (xc.shape[1] if xkv.kv_off is None else xkv.longest) > LONG_KEYS     # more keys than ops.attention takes
+            if xkv.kv_off is None and xlong:
+                ctx = ops.attention_long(q.view(n, 1, d.inner), xc[:, :, :d.inner], xc[:, :, d.inner:], d.num_heads,
+                                         kv_div=kv_div, key_mask=xkv.mask)
+            elif xkv.kv_off is None:
                 ctx = ops.attention(q.view(n, 1, d.inner), xc[:, :, :d.inner], xc[:, :, d.inner:], d.num_heads,
                                     kv_div=kv_div, key_mask=xkv.mask, split_bound=L["xvb"])
+            elif xlong:
+                ctx = ops.attention_long(q.view(n, 1, d.inner), xc[:, :d.inner], xc[:, d.inner:], d.num_heads, kv_div=kv_div,
+                                         kv_off=xkv.kv_off, kv_longest=xkv.longest)
             else:
                 ctx = ops.attention(q.view(n, 1, d.inner), xc[:, :d.inner], xc[:, d.inner:], d.num_heads, kv_div=kv_div,
                                     kv_off=xkv.kv_off, kv_longest=xkv.longest, split_bound=L["xvb"])
-            x = self._rl(ctx if L["xvb"] is not None else ctx.view(n, d.inner), L, "xo", x)
+            x = self._rl(ctx if L["xvb"] is not None and not xlong else ctx.view(n, d.inner), L, "xo", x)
             x = self._rl(self._nl(x, L, "ln2", "wi", relu=True, for_gemm=True), L, "wo2", x)
         return self._final(x)
 

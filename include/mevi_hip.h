@@ -767,11 +767,23 @@ typedef struct mevi_ip_topk_stats {
    * was searched again through the f16 image; the other fields then describe both searches) */
   int64_t n_i8_queries;
   int64_t n_i8_unproven;
+  /* main pass: filter launches that ran under a threshold predicted from a rank of the rows seen (mevi_ip_topk_plan: rank > 0),
+   * and the design effect D the pass measured on its last exact launch before them (variance / mean of the keys appended per
+   * query, relative to exchangeable row order; 0: not measured -- small batches, the exact-f32 and the 8-bit search) */
+  int64_t n_predicted_launches;
+  double dispersion;
 } mevi_ip_topk_stats;
 /* The tile walk of the large-batch f16 filter (host arithmetic, no device work): the (corpus tile pair, query tile) items that
  * workgroup label `label` (blockIdx & 7) takes, in ticket order, for n_dpairs x n_qtiles items.  Writes them when both arrays are
  * non-null; returns how many there are, -1 on bad arguments. */
 int64_t mevi_ip_filter_tile_walk(int64_t n_dpairs, int64_t n_qtiles, int label, int32_t *dpair, int32_t *qtile);
+/* The launch schedule of the f16-image pass of mevi_ip_topk_indexed_f32 (host arithmetic, no device work; the function the pass
+ * itself calls): nq queries, nd rows, lists of kprime keys with a candidate area of cap slots, design effect `dispersion` of the
+ * row order (1: exchangeable).  Per launch: its rows, the rank of the kept list whose key is the launch's predicted threshold
+ * (0: the exact threshold, the kprime-th key), and the keys it is expected to append per query.  Writes the first max_launches
+ * entries of every non-null array; returns the number of launches, -1 on bad arguments. */
+int64_t mevi_ip_topk_plan(int64_t nq, int64_t nd, int64_t kprime, int64_t cap, double dispersion, int64_t max_launches,
+                          int64_t *rows, int32_t *rank, double *expect_keys);
 void mevi_ip_topk_set_growth(double growth);
 void mevi_ip_topk_set_profiling(int enable); /* 1: record HIP events around every filter/compact launch; 2: also count candidates */
 void mevi_ip_topk_get_stats(mevi_ip_topk_stats *out);

@@ -708,6 +708,8 @@ __global__ __launch_bounds__(256) void rank_tau_kernel(const unsigned long long 
   for (int j = 0; j < KPL; ++j) key[j] = (64 * j + lane < k) ? row[64 * j + lane] : 0ull;
   const int nj = (k + 63) >> 6;
   unsigned long long T = 0ull;     // the largest T with at least `rank` keys >= T = the rank-th largest key
+  bool exact = false;              // exactly `rank` keys >= T: their minimum is that key (compact_wave_kernel's early stop --
+                                   // after ~25 of the 64 bits on a list of distinct scores; a pass calls this once per prediction)
   for (int b = 63; b >= 0; --b) {
     const unsigned long long cand = T | (1ull << b);
     int cnt = 0;
@@ -717,7 +719,32 @@ __global__ __launch_bounds__(256) void rank_tau_kernel(const unsigned long long 
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) cnt += __popcll(__ballot(key[8 * jb + jj] >= cand));
       }
-    if (cnt >= rank) T = cand;
+    if (cnt >= rank) {
+      T = cand;
+      if (cnt == rank) {
+        exact = true;
+        break;
+      }
+    }
+  }
+  if (exact) {
+    unsigned long long mn = ~0ull;
+#pragma unroll
+    for (int jb = 0; jb < KPL / 8; ++jb)
+      if (8 * jb < nj) {
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) {
+          const unsigned long long kk = key[8 * jb + jj];
+          if (kk >= T && kk < mn) mn = kk;
+        }
+      }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long o = ((unsigned long long)(unsigned int)__shfl_xor((int)(mn >> 32), off) << 32) |
+                                   (unsigned int)__shfl_xor((int)mn, off);
+      mn = o < mn ? o : mn;
+    }
+    T = mn;
   }
   if (lane == 0) {
     const float t = (T != 0ull) ? key_score(T) : -INFINITY;   // fewer than `rank` rows so far: no threshold, nothing is dropped
@@ -1863,6 +1890,24 @@ __global__ __launch_bounds__(256) void count_candidates_kernel(const unsigned in
   }
 }
 
+// Dispersion of a launch's appends (run_pass, predicted thresholds): out[0] += sum over queries of count, out[1] += sum of
+// count^2, before the compaction resets the counts.  (count <= ~2^24, nq < 2^31: the sums fit 64 bits.)
+__global__ __launch_bounds__(256) void count_moments_kernel(const unsigned int *__restrict__ count, int nq,
+                                                           unsigned long long *__restrict__ out) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long c = q < nq ? count[q] : 0u;
+  unsigned long long s1 = c, s2 = c * c;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s1 += ((unsigned long long)(unsigned int)__shfl_xor((int)(s1 >> 32), off) << 32) | (unsigned int)__shfl_xor((int)s1, off);
+    s2 += ((unsigned long long)(unsigned int)__shfl_xor((int)(s2 >> 32), off) << 32) | (unsigned int)__shfl_xor((int)s2, off);
+  }
+  if ((threadIdx.x & 63) == 0 && s1 != 0ull) {
+    atomicAdd(out, s1);
+    atomicAdd(out + 1, s2);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Workspace layouts.  Every layout is a struct (members in memory order) with ONE function that fills it from a Carver and a
 // shape; its size is that same function run over a null base (carved_bytes), so byte count and pointers cannot drift apart.
@@ -1926,7 +1971,7 @@ static QuerySide carve_query_side(Carver &c, int64_t nq, size_t image_bytes) {
 
 thread_local double g_growth = 0.0;
 thread_local int g_profile = 0;
-thread_local mevi_ip_topk_stats g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
+thread_local mevi_ip_topk_stats g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0.0};
 thread_local std::vector<hipEvent_t> g_events;  // triples: before filter, after filter, after compact
 thread_local std::vector<long long> g_chunk_rows;  // rows of the launch each triple brackets (profiling on)
 
@@ -1965,7 +2010,194 @@ struct PassArgs {
   bool guaranteed;               // every chunk fits the candidate area: no query can overflow
   unsigned long long *cand = nullptr;                 // the candidate counters of profiling level 2
   const float *row_scale = nullptr, *qub = nullptr;   // I8Image only: per-row scales, the queries' G_q
+  unsigned long long *moments = nullptr;              // [2], zeroed: the main f16 pass of an indexed search may predict its
+                                                      // thresholds (plan_pass) and measures the dispersion of its appends here
 };
+
+// ---- the launch schedule of a pass (host arithmetic; run_pass walks it, mevi_ip_topk_plan shows it) ----------------------------
+struct PlanLaunch {
+  int64_t rows;   // tile aligned but for the corpus' last launch
+  int rank;       // 0: the launch runs under the exact threshold (the k-th key of the list); r > 0: under the r-th key
+  double expect;  // keys the launch is expected to append per query (flush cadence, candidate area)
+};
+struct PlanShape {
+  int64_t nq, nd;
+  int k, cap;       // list length of the pass (K' of an f16 pass), candidate slots
+  bool guaranteed;  // no chunk larger than the candidate area
+  bool predict;     // thresholds predicted launch by launch are allowed (large batches of the f16 pass; spec_tau_on())
+  double D;         // design effect of the row order (predict only): a prefix of n rows ranks like n / D exchangeable ones
+};
+
+// MEVI_IP_SPEC_TAU=0: no predicted thresholds for large batches, the geometric schedule to the end (A/B; same lists)
+static bool spec_tau_on() {
+  static const bool on = [] { const char *e = getenv("MEVI_IP_SPEC_TAU"); return !(e && atoi(e) == 0); }();
+  return on;
+}
+// rows a large batch has to have seen before it measures D and predicts (MEVI_IP_SPEC_MIN_SEEN: tuning hook, unset in production)
+static int64_t spec_min_seen() {
+  static const int64_t v = [] { const char *e = getenv("MEVI_IP_SPEC_MIN_SEEN"); const long long x = e ? atoll(e) : 0; return x >= 1000 ? (int64_t)x : (int64_t)50000; }();
+  return v;
+}
+constexpr double SPEC_D_NONE = 64.0;       // from this design effect on a prefix predicts too little to be asked
+// Cost of the rest of a schedule, for choosing how many predicted launches take it: every launch pays T_LAUNCH_MS whatever
+// its size and T_KEY_MS per key it appends, over and above its rows.  Fitted to a trace of the geometric schedule at 6980
+// queries (profiles/r07_predicted_tau.txt): t = 8.19 us per 1000 rows + c from its two largest launches; c = 0.61 ms at 1280
+// appended keys per query and 0.41 ms at 319 (the short last launch) = 30 ps per key -- a device-wide rate, the appends of all
+// CUs overlap -- and 0.34 ms of fixed filter cost + 0.10 ms of compaction per launch.  (The 60 ns of the growth model in
+// plan_pass is the latency of ONE append, multiplied there by every key of the batch: 536 ms per unit of growth at 6980 x
+// 1280, so that model returns its smallest candidate for every large batch.)
+constexpr double T_KEY_MS = 30e-9, T_LAUNCH_MS = 0.44;
+
+// smallest z with nq * launches * Phi(-z) <= 1e-3: the failure budget of a search's predicted launches
+static double spec_z(int64_t nq, int launches) {
+  const double budget = 1e-3 / ((double)nq * (double)launches);
+  double lo = 0.0, hi = 12.0;
+  for (int i = 0; i < 60; ++i) {
+    const double mid = 0.5 * (lo + hi);
+    (0.5 * erfc(mid / sqrt(2.0)) <= budget ? hi : lo) = mid;
+  }
+  return hi;
+}
+
+// One predicted launch of `chunk` rows after `seen`: the smallest c_s >= 1.15 (in steps of 0.01) with
+//   r = ceil(c_s k seen / (seen + chunk)),   (1 - 1 / c_s) sqrt(r / D) >= z,   c_s k (1 + z sqrt(D / r)) <= cap,
+// i.e. the list is expected to hold c_s k keys above the r-th key of the rows seen, z deviations of that estimate above the k
+// it needs and z below what the candidate area takes.  False: none, the launch runs under the exact threshold.
+static bool spec_launch(int64_t seen, int64_t chunk, int k, int cap, double D, double z, PlanLaunch &out) {
+  const double frac = (double)seen / (double)(seen + chunk);
+  for (double c = 1.15; c * (double)k <= (double)cap; c += 0.01) {
+    const double r = ceil(c * (double)k * frac);
+    if (r < 16.0 || r > (double)k) continue;
+    if ((1.0 - 1.0 / c) * sqrt(r / D) < z) continue;
+    if (c * (double)k * (1.0 + z * sqrt(D / r)) > (double)cap) return false;   // (grows with c: no larger c fits either)
+    // the appends of most queries (two deviations) stay within what compact_wave_kernel<64> takes with the list, where the
+    // exact launch this one replaces does: measured on the clustered corpus (D ~ 10), three launches of 2945 expected keys
+    // left a third of the queries to compact_kernel, 0.38 instead of 0.10 ms per launch -- more than the launches saved
+    const double appended = c * (double)k * (1.0 - frac);
+    if (2 * k <= 64 * 64 && (double)k + appended * (1.0 + 2.0 * sqrt(D / r)) > 64.0 * 64.0) return false;
+    out = {chunk, (int)r, appended};
+    return true;
+  }
+  return false;
+}
+
+static std::vector<PlanLaunch> plan_pass(const PlanShape &p) {
+  const int64_t nq = p.nq, nd = p.nd;
+  const int k = p.k, cap = p.cap;
+  const bool guaranteed = p.guaranteed;
+  // expected survivors per chunk = k * growth = cap / growth_div (default 3: 3x head-room over the mean, tens of standard
+  // deviations for exchangeable row order; a query that still overflows takes the guaranteed path)
+  double growth_div = 3.0;
+  if (const char *e = getenv("MEVI_IP_TOPK_GROWTH_DIV")) {  // tuning hook, unset in production
+    const double v = atof(e);
+    if (v >= 1.05 && v <= 64.0) growth_div = v;
+  }
+  double growth = g_growth > 0.0 ? g_growth : (double)cap / (growth_div * k);
+  if (growth < 1.0) growth = 1.0;
+  // Round 6: the growth the candidate area ALLOWS is not always the growth that is cheapest.  A launch whose chunk is g x the rows
+  // seen appends ~k g keys per query, and the pass needs ln(nd / first) / ln(1 + g) launches, so
+  //     cost(g) ~ (nq k t_key g + t_launch) / ln(1 + g),   t_key ~ 60 ns per appended key, t_launch ~ 0.2 ms (launch + compaction)
+  // (measured on the C2 search, profiles/r06_filter_launches.txt: growth 1.8 -> 1.0 = 8 -> 12 launches, 22.8 k -> 20.0 k keys per
+  // query, 88.6 -> 87.0 and 87.9 -> 87.0 ms on two boxes).  Large batches with long lists want g ~ 1, everything else the
+  // largest g its area allows (shards of a W-way search, small batches: launches dominate).  Not under the tuning hooks.
+  // (The constants are those of one append, not of the device -- see T_KEY_MS; they stay because the schedules of small batches
+  // and of the exact-f32 search are what they select, and g = 1 for the exact launches of a large batch is what the sweep above
+  // measured as fastest.  What a large batch does AFTER its exact launches is decided with the fitted constants below.)
+  if (g_growth <= 0.0 && !getenv("MEVI_IP_TOPK_GROWTH_DIV") && !guaranteed) {
+    const double keys = (double)nq * (double)k * 60e-9 * 1e3, t_launch = 0.2;       // ms per unit g, ms per launch
+    double best = growth, best_cost = (keys * growth + t_launch) / log(1.0 + growth);
+    for (double cand = 1.0; cand < growth; cand += 0.25) {
+      const double c = (keys * cand + t_launch) / log(1.0 + cand);
+      if (c < best_cost * 0.99) best = cand, best_cost = c;                            // (ties go to fewer launches)
+    }
+    growth = best;
+  }
+  int64_t cap_docs = (cap / (2 * BM)) * (2 * BM);  // chunk that can never overflow, tile aligned
+  if (const char *e = getenv("MEVI_IP_TOPK_FIRST_CHUNK")) {  // tuning hook (rows of the first chunk, <= the candidate area), unset in production
+    const int64_t v = atoll(e) / (2 * BM) * (2 * BM);
+    if (v >= 2 * BM && v < cap_docs) cap_docs = v;
+  }
+  // sampled threshold for the pass's LAST launch (rank_tau_kernel above).  r ranks give the estimate +-1/sqrt(r); the launch is
+  // sized for c k expected keys per query with (1 - 1/c) sqrt(r) >= 4.5 deviations between that and the k it needs, and
+  // c k (1 + 8 / sqrt(r)) inside the candidate area.  MEVI_IP_SAMPLE_TAU=0: the geometric schedule to the end (A/B; same lists).
+  // Used for searches of up to 1024 queries (MEVI_IP_SAMPLE_TAU=1: any size): measured on one box (profiles/r06_sampled_threshold.txt)
+  // 64 / 128 / 255 queries at top-1000 3.54 / 3.56 / 4.46 -> 3.23 / 3.32 / 4.24 ms; at 6980 queries the launches it merges are
+  // matrix-bound already (-0.8 ms of 88) and on a corpus whose clusters sit in runs of adjacent rows the estimate's variance is
+  // that of ~r / 8 ranks: ~10 of 6980 queries are flagged, and their second pass (+2.3 ms) costs more than the merge returns.
+  // Larger batches of the f16 pass predict launch by launch instead, with the margin their measured dispersion asks for (below).
+  static const int sample_mode = [] { const char *e = getenv("MEVI_IP_SAMPLE_TAU"); return e ? atoi(e) : -1; }();
+  const bool sample_on = sample_mode == 1 || (sample_mode != 0 && nq <= 1024);
+  double s_c = 0.0;
+  int64_t n_sample = 0;
+  bool sampled = false;
+  if (sample_on && !guaranteed && k <= 4096 && k >= 32) {
+    const double r = k / 2 < 16 ? 16.0 : (k / 2 > 96 ? 96.0 : (double)(k / 2));
+    double c = r >= 96.0 ? 3.0 : 8.0;
+    const double c_fit = (double)cap / ((double)k * (1.0 + 8.0 / sqrt(r)));
+    if (c_fit < c) c = c_fit;
+    if (c >= 1.5 && (1.0 - 1.0 / c) * sqrt(r) >= 4.5) {
+      s_c = c;
+      n_sample = (int64_t)ceil(r * (double)nd / (c * (double)k));
+    }
+  }
+  // Predicted thresholds, launch by launch (large batches; DESIGN 4.1b'): once spec_min_seen() rows are in, n equal steps of
+  // chunk = G seen take the rest, G = (nd / seen)^(1/n) - 1, each under the r-th key of the list (spec_launch).  n is the
+  // cheapest count that qualifies (cost: T_KEY_MS, T_LAUNCH_MS) and must beat the exact schedule's in launches and in cost;
+  // the failure budget z is that of the n launches chosen.
+  const bool predict = p.predict && !sample_on && !guaranteed && nq > 1024 && k >= 32 && k <= 4096 && p.D < SPEC_D_NONE && p.D >= 1.0;
+  int spec_left = -1;   // predicted launches still to come; -1: not decided yet
+  double spec_zv = 0.0;
+  std::vector<PlanLaunch> plan;
+  int64_t seen = 0;
+  while (seen < nd) {
+    int64_t chunk = cap_docs;
+    if (!guaranteed && seen >= k) {
+      int64_t grown = (int64_t)((double)seen * growth);
+      grown = grown / (2 * BM) * (2 * BM);
+      if (grown > chunk) chunk = grown;
+    }
+    if (chunk > nd - seen) chunk = nd - seen;
+    PlanLaunch l = {chunk, 0, seen >= k ? (double)k * (double)chunk / (double)seen : (double)chunk};
+    if (s_c > 0.0 && !sampled && seen >= n_sample && seen >= k && chunk < nd - seen) {
+      // enough rows are in and the schedule would need more than one further launch: estimate, then everything that is left
+      const int64_t rank = (int64_t)ceil(s_c * (double)k * (double)seen / (double)nd);
+      if (rank >= 16 && rank <= k) {
+        sampled = true;
+        l = {nd - seen, (int)rank, s_c * (double)k};
+      }
+    }
+    if (predict && seen >= spec_min_seen() && seen >= k && chunk < nd - seen) {
+      const double ratio = (double)nd / (double)seen;
+      const auto step = [&](int n_left) {   // rows of the next of n_left equal steps
+        if (n_left <= 1) return nd - seen;
+        const int64_t c = (int64_t)((double)seen * (pow(ratio, 1.0 / n_left) - 1.0)) / (2 * BM) * (2 * BM);
+        return c < nd - seen ? c : nd - seen;
+      };
+      if (spec_left < 0) {
+        spec_left = 0;
+        const int n_exact = (int)ceil(log(ratio) / log(1.0 + (double)chunk / (double)seen));
+        double best_cost = (double)n_exact * ((double)nq * l.expect * T_KEY_MS + T_LAUNCH_MS);
+        for (int n = 1; n < n_exact; ++n) {
+          const double z = spec_z(nq, n);
+          PlanLaunch t;
+          const int64_t c = step(n);
+          if (c < 2 * BM || !spec_launch(seen, c, k, cap, p.D, z, t)) continue;
+          const double cost = (double)n * ((double)nq * t.expect * T_KEY_MS + T_LAUNCH_MS);
+          if (cost < best_cost) best_cost = cost, spec_left = n, spec_zv = z;
+        }
+      }
+      if (spec_left > 0) {
+        PlanLaunch t;
+        const int64_t c = step(spec_left);
+        if (c >= 2 * BM && spec_launch(seen, c, k, cap, p.D, spec_zv, t)) l = t;   // (else: this one under the exact threshold)
+        if (l.rows == c) --spec_left;
+      }
+    }
+    plan.push_back(l);
+    seen += l.rows;
+  }
+  return plan;
+}
 
 // per (doc-tile pair, query tile) / persistent, one workgroup per CU / one per CU, each walking 256-row blocks of the chunk
 enum class FilterGrid { PerTile, PerCU, SmallStream };
@@ -2050,35 +2282,6 @@ static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
   FilterChoice f;
   if (!choose_filter(a.kind, nq, a.dim, f)) return -1;
   const int n_qtiles = (int)((nq + f.qt - 1) / f.qt);
-  // expected survivors per chunk = k * growth = cap / growth_div (default 3: 3x head-room over the mean, tens of standard
-  // deviations for exchangeable row order; a query that still overflows takes the guaranteed path)
-  double growth_div = 3.0;
-  if (const char *e = getenv("MEVI_IP_TOPK_GROWTH_DIV")) {  // tuning hook, unset in production
-    const double v = atof(e);
-    if (v >= 1.05 && v <= 64.0) growth_div = v;
-  }
-  double growth = g_growth > 0.0 ? g_growth : (double)g.cap / (growth_div * g.k);
-  if (growth < 1.0) growth = 1.0;
-  // Round 6: the growth the candidate area ALLOWS is not always the growth that is cheapest.  A launch whose chunk is g x the rows
-  // seen appends ~k g keys per query, and the pass needs ln(nd / first) / ln(1 + g) launches, so
-  //     cost(g) ~ (nq k t_key g + t_launch) / ln(1 + g),   t_key ~ 60 ns per appended key, t_launch ~ 0.2 ms (launch + compaction)
-  // (measured on the C2 search, profiles/r06_filter_launches.txt: growth 1.8 -> 1.0 = 8 -> 12 launches, 22.8 k -> 20.0 k keys per
-  // query, 88.6 -> 87.0 and 87.9 -> 87.0 ms on two boxes).  Large batches with long lists want g ~ 1, everything else the
-  // largest g its area allows (shards of a W-way search, small batches: launches dominate).  Not under the tuning hooks.
-  if (g_growth <= 0.0 && !getenv("MEVI_IP_TOPK_GROWTH_DIV") && !guaranteed) {
-    const double keys = (double)nq * (double)g.k * 60e-9 * 1e3, t_launch = 0.2;       // ms per unit g, ms per launch
-    double best = growth, best_cost = (keys * growth + t_launch) / log(1.0 + growth);
-    for (double cand = 1.0; cand < growth; cand += 0.25) {
-      const double c = (keys * cand + t_launch) / log(1.0 + cand);
-      if (c < best_cost * 0.99) best = cand, best_cost = c;                            // (ties go to fewer launches)
-    }
-    growth = best;
-  }
-  int64_t cap_docs = (g.cap / (2 * BM)) * (2 * BM);  // chunk that can never overflow, tile aligned
-  if (const char *e = getenv("MEVI_IP_TOPK_FIRST_CHUNK")) {  // tuning hook (rows of the first chunk, <= the candidate area), unset in production
-    const int64_t v = atoll(e) / (2 * BM) * (2 * BM);
-    if (v >= 2 * BM && v < cap_docs) cap_docs = v;
-  }
   // opt in to > 64 KiB dynamic LDS (per device; cheap, so done on every call)
   if (hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds) != hipSuccess) {
     set_error("ip_topk: cannot raise dynamic LDS to %zu bytes", f.lds);
@@ -2095,48 +2298,50 @@ static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
   // leaving the rest to whatever else is in flight (a second search's re-scoring on another stream)
   static const int cu_cap = [] { const char *e = getenv("MEVI_IP_FILTER_CUS"); return e ? atoi(e) : 0; }();
   if (cu_cap >= 8 && cu_cap < n_cu) n_cu = cu_cap / 8 * 8;
-  // sampled threshold for the pass's LAST launch (rank_tau_kernel above).  r ranks give the estimate +-1/sqrt(r); the launch is
-  // sized for c k expected keys per query with (1 - 1/c) sqrt(r) >= 4.5 deviations between that and the k it needs, and
-  // c k (1 + 8 / sqrt(r)) inside the candidate area.  MEVI_IP_SAMPLE_TAU=0: the geometric schedule to the end (A/B; same lists).
-  // Used for searches of up to 1024 queries (MEVI_IP_SAMPLE_TAU=1: any size): measured on one box (profiles/r06_sampled_threshold.txt)
-  // 64 / 128 / 255 queries at top-1000 3.54 / 3.56 / 4.46 -> 3.23 / 3.32 / 4.24 ms; at 6980 queries the launches it merges are
-  // matrix-bound already (-0.8 ms of 88) and on a corpus whose clusters sit in runs of adjacent rows the estimate's variance is
-  // that of ~r / 8 ranks: ~10 of 6980 queries are flagged, and their second pass (+2.3 ms) costs more than the merge returns.
-  static const int sample_mode = [] { const char *e = getenv("MEVI_IP_SAMPLE_TAU"); return e ? atoi(e) : -1; }();
-  const bool sample_on = sample_mode == 1 || (sample_mode != 0 && nq <= 1024);
-  double s_c = 0.0;
-  int64_t n_sample = 0;
-  bool sampled = false;
-  if (sample_on && !guaranteed && g.k <= 4096 && g.k >= 32) {
-    const double r = g.k / 2 < 16 ? 16.0 : (g.k / 2 > 96 ? 96.0 : (double)(g.k / 2));
-    double c = r >= 96.0 ? 3.0 : 8.0;
-    const double c_fit = (double)g.cap / ((double)g.k * (1.0 + 8.0 / sqrt(r)));
-    if (c_fit < c) c = c_fit;
-    if (c >= 1.5 && (1.0 - 1.0 / c) * sqrt(r) >= 4.5) {
-      s_c = c;
-      n_sample = (int64_t)ceil(r * (double)nd / (c * (double)g.k));
-    }
+  // The schedule (plan_pass).  A pass that may predict its thresholds starts on the plan without predictions (D unknown), measures
+  // D on the first launch that takes it past spec_min_seen() rows -- the sums of count and count^2 over the queries, read back
+  // after that launch's compaction: 16 bytes behind one stream synchronise where launches take 0.1-0.3 ms -- and plans again:
+  // the launches up to there are the same in every plan.  Under exchangeable row order a launch of m rows after n appends
+  // counts of variance / mean = 1 + m / n (Poisson around a threshold that is itself the k-th of n: its tail mass varies by
+  // 1 / sqrt(k)); D is the measured ratio over that, at least 1.  MEVI_IP_SPEC_D=<D>: no measurement, this D (probe: what the
+  // read-back costs; tests).
+  PlanShape shape = {nq, nd, g.k, g.cap, guaranteed, a.kind == PassKind::F16Image && a.moments && spec_tau_on(), 1e30};
+  static const double d_pin = [] { const char *e = getenv("MEVI_IP_SPEC_D"); return e ? atof(e) : 0.0; }();
+  if (shape.predict && d_pin >= 1.0) shape.D = d_pin;
+  std::vector<PlanLaunch> plan = plan_pass(shape);
+  int64_t measure_at = -1;
+  if (shape.predict && !(d_pin >= 1.0)) {
+    int64_t s = 0;
+    for (size_t i = 0; i + 1 < plan.size(); s += plan[i++].rows)
+      if (s + plan[i].rows >= spec_min_seen()) {
+        if (s >= g.k && plan[i].rank == 0) measure_at = (int64_t)i;
+        break;
+      }
   }
+  if (shape.predict) g_stats.dispersion = d_pin >= 1.0 ? d_pin : 0.0;
+  static const bool trace = getenv("MEVI_IP_TOPK_TRACE") != nullptr;
+  const auto trace_plan = [&](const char *what) {
+    if (!trace) return;
+    int64_t s = 0;
+    for (size_t i = 0; i < plan.size(); s += plan[i++].rows)
+      fprintf(stderr, "ip_topk plan (%s, D = %.3g) launch %zu: rows %lld -> %lld  rank %d  expected keys %.0f\n", what,
+              shape.predict ? shape.D : 0.0, i, (long long)s, (long long)(s + plan[i].rows), plan[i].rank, plan[i].expect);
+  };
+  trace_plan(shape.predict && measure_at >= 0 ? "before D" : "final");
   int64_t seen = 0, launches = 0;
   while (seen < nd) {
-    int64_t chunk = cap_docs;
-    if (!guaranteed && seen >= g.k) {
-      int64_t grown = (int64_t)((double)seen * growth);
-      grown = grown / (2 * BM) * (2 * BM);
-      if (grown > chunk) chunk = grown;
+    if ((size_t)launches >= plan.size()) {
+      set_error("ip_topk: the launch plan ends at row %lld of %lld", (long long)seen, (long long)nd);
+      return -1;
     }
-    if (chunk > nd - seen) chunk = nd - seen;
-    double expect_per_q = seen >= g.k ? (double)g.k * (double)chunk / (double)seen : (double)chunk;
-    if (s_c > 0.0 && !sampled && seen >= n_sample && seen >= g.k && chunk < nd - seen) {
-      // enough rows are in and the schedule would need more than one further launch: estimate, then everything that is left
-      const int64_t rank = (int64_t)ceil(s_c * (double)g.k * (double)seen / (double)nd);
-      if (rank >= 16 && rank <= g.k) {
-        hipLaunchKernelGGL(rank_tau_kernel<64>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, st.buf, (int)nq, g.S, g.k, (int)rank,
-                           st.tau, st.tau_s);
-        sampled = true;
-        chunk = nd - seen;
-        expect_per_q = s_c * (double)g.k;
-      }
+    const PlanLaunch pl = plan[(size_t)launches];
+    const int64_t chunk = pl.rows;
+    const double expect_per_q = pl.expect;
+    const bool predicted = pl.rank > 0;
+    if (predicted) {  // tau = tau_s = the rank-th key of the list: the launch drops every row that does not beat it
+      hipLaunchKernelGGL(rank_tau_kernel<64>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, st.buf, (int)nq, g.S, g.k, pl.rank,
+                         st.tau, st.tau_s);
+      ++g_stats.n_predicted_launches;
     }
     const int64_t n_dtiles = (chunk + 2 * BM - 1) / (2 * BM);  // doc-tile pairs (ping-pong kernel)
     const int64_t nwg = n_dtiles * n_qtiles;
@@ -2190,6 +2395,8 @@ static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
     profile_mark(stream);
     if (a.cand)
       hipLaunchKernelGGL(count_candidates_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, st.count, (int)nq, g.cap, a.cand);
+    if (launches == measure_at)
+      hipLaunchKernelGGL(count_moments_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, st.count, (int)nq, a.moments);
     {
       const int nq_i = (int)nq;
       // one wave per query with the keys in registers first (MEVI_IP_TOPK_COMPACT=lds: the LDS kernel alone); what it leaves
@@ -2201,13 +2408,33 @@ static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
       hipLaunchKernelGGL(compact_kernel, dim3((unsigned)(nq < 8 * n_cu ? nq : 8 * n_cu)), dim3(256), compact_lds, stream,
                          st.buf, st.count, st.tau, st.failed, nq_i, g.S, g.k, g.cap);
     }
-    if (sampled && seen + chunk >= nd)   // the sampled launch was the last: did k rows beat its threshold?
+    if (predicted)   // did k rows beat the predicted threshold?  (before the next prediction overwrites tau_s)
       hipLaunchKernelGGL(sample_check_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, st.tau, st.tau_s, st.failed, (int)nq);
     profile_mark(stream);
     g_stats.filter_flops += 2.0 * (double)nq * (double)chunk * (double)a.dim;
     if (g_profile) g_chunk_rows.push_back((long long)chunk);
     seen += chunk;
     ++launches;
+    if (launches - 1 == measure_at) {
+      unsigned long long m[2] = {0ull, 0ull};
+      if (hipMemcpyAsync(m, a.moments, sizeof(m), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+          hipStreamSynchronize(stream) != hipSuccess) {
+        set_error("ip_topk: reading the dispersion sums failed");
+        return -1;
+      }
+      const double mean = (double)m[0] / (double)nq, var = (double)m[1] / (double)nq - mean * mean;
+      const double ratio = mean >= 1.0 ? var / mean / (1.0 + (double)chunk / (double)(seen - chunk)) : 1e30;  // (nothing appended: no basis)
+      shape.D = ratio > 1.0 ? ratio : 1.0;
+      g_stats.dispersion = shape.D;
+      plan = plan_pass(shape);
+      trace_plan("final");
+      int64_t s = 0;
+      for (size_t i = 0; i < (size_t)launches && i < plan.size(); ++i) s += plan[i].rows;
+      if (s != seen) {
+        set_error("ip_topk: the launch plan changed behind row %lld", (long long)seen);
+        return -1;
+      }
+    }
   }
   if (a.kind == PassKind::ExactF32)  // exact passes hand their lists out as ranked results (the f16 pass is re-scored and sorted later)
     hipLaunchKernelGGL(sort_lists_kernel, dim3((unsigned)nq), dim3(256), (size_t)next_pow2(g.k < 64 ? 64 : g.k) * 8, stream,
@@ -2226,7 +2453,7 @@ static void finalize(const unsigned long long *lists, int ld, int64_t k, int64_t
 
 // Every search entry point starts its statistics (and the profiling events a failed call may have left) from nothing.
 static void begin_call() {
-  g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
+  g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0.0};
   for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
   g_events.clear();
 }
@@ -2292,6 +2519,19 @@ extern "C" int64_t mevi_ip_filter_tile_walk(int64_t n_dpairs, int64_t n_qtiles, 
     qtile[t] = b;
   }
   return len;
+}
+
+extern "C" int64_t mevi_ip_topk_plan(int64_t nq, int64_t nd, int64_t kprime, int64_t cap, double dispersion, int64_t max_launches,
+                                     int64_t *rows, int32_t *rank, double *expect_keys) {
+  if (nq <= 0 || nd < 0 || kprime <= 0 || kprime > MAX_SORT || cap < 2 * BM || cap > MAX_SORT || !(dispersion >= 1.0) || max_launches < 0)
+    return -1;
+  const std::vector<PlanLaunch> plan = plan_pass({nq, nd, (int)kprime, (int)cap, false, spec_tau_on(), dispersion});
+  for (size_t i = 0; i < plan.size() && (int64_t)i < max_launches; ++i) {
+    if (rows) rows[i] = plan[i].rows;
+    if (rank) rank[i] = plan[i].rank;
+    if (expect_keys) expect_keys[i] = plan[i].expect;
+  }
+  return (int64_t)plan.size();
 }
 
 extern "C" void mevi_ip_topk_set_growth(double growth) { g_growth = growth; }
@@ -2499,11 +2739,14 @@ extern "C" int mevi_ip_topk_indexed_f32(const float *q, int64_t nq, const float 
   const float c1 = h1_cacc(dimp), c2 = h1_c2(dim);   // c1: the accumulation constant of h1_err_bound (the roundings are measured)
   unsigned long long *cand = g_profile >= 2 ? w.counters : nullptr;
   if (cand) MEVI_HIP_CHECK(hipMemsetAsync(cand, 0, 32, stream));
+  unsigned long long *const moments = w.counters + 4;  // (the same 256-byte slot, behind the three counters)
+  MEVI_HIP_CHECK(hipMemsetAsync(moments, 0, 16, stream));
 
   hipLaunchKernelGGL(split_queries_f16_kernel, dim3((unsigned)(image_rows(nq) / 4)), dim3(256), 0, stream, q, (long long)nq,
                      (int)dim, (int)dimp, iv.mu, iv.scal, reinterpret_cast<_Float16 *>(qs.image), qs.norm, qs.inv, qs.shift, qs.delta,
                      qs.n16);
-  int64_t launches = run_pass({PassKind::F16Image, qs.image, nq, iv.image, nd, (int)dimp, gp, (uint32_t)id_offset, st, false, cand}, stream);
+  int64_t launches = run_pass({PassKind::F16Image, qs.image, nq, iv.image, nd, (int)dimp, gp, (uint32_t)id_offset, st, false, cand,
+                               nullptr, nullptr, moments}, stream);
   if (launches < 0) return MEVI_ERR_HIP;
   g_stats.n_chunks = launches;
   g_stats.filter_flops *= (double)dim / (double)dimp;  // algorithmic flops count dim, not the padding
@@ -2564,8 +2807,10 @@ extern "C" int mevi_ip_topk_indexed_f32(const float *q, int64_t nq, const float 
                        (int)dim, (int)dimp, iv.mu, iv.scal, reinterpret_cast<_Float16 *>(qs2.image), qs2.norm, qs2.inv, qs2.shift,
                        qs2.delta, qs2.n16);
     const double keep_flops = g_stats.filter_flops;
+    const int64_t keep_predicted = g_stats.n_predicted_launches;
     const int64_t l2 = run_pass({PassKind::F16Image, qs2.image, n2, iv.image, nd, (int)dimp, g2, (uint32_t)id_offset, s2, false}, stream);
     g_stats.filter_flops = keep_flops;
+    g_stats.n_predicted_launches = keep_predicted;
     if (l2 < 0) return MEVI_ERR_HIP;
     prove(w.q2, docs, n2, dim, k, g2, (uint32_t)id_offset, s2, qs2, w.second.top, c1, c2, iv.bits, iv.norms_c, nullptr, nullptr, 0,
           stream);

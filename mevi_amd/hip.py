@@ -23,7 +23,8 @@ class IpTopkStats(ctypes.Structure):
                 ("filter_ms", c_double), ("compact_ms", c_double), ("filter_flops", c_double),
                 ("max_err_ratio", c_double), ("err_bound", c_double), ("n_second_pass_queries", c_int64),
                 ("n_filter_candidates", c_int64), ("max_launch_candidates", c_int64), ("n_list_overflows", c_int64),
-                ("n_i8_queries", c_int64), ("n_i8_unproven", c_int64)]
+                ("n_i8_queries", c_int64), ("n_i8_unproven", c_int64),
+                ("n_predicted_launches", c_int64), ("dispersion", c_double)]
 
 
 _SIGNATURES = {
@@ -181,6 +182,7 @@ _SIGNATURES = {
     "mevi_ip_filter_tile_walk": (c_int64, [c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "mevi_ip_topk_set_growth": (None, [c_double]),
     "mevi_ip_topk_set_profiling": (None, [c_int]),
+    "mevi_ip_topk_plan": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_double, c_int64, c_void_p, c_void_p, c_void_p]),
     "mevi_ip_topk_get_stats": (None, [ctypes.POINTER(IpTopkStats)]),
 }
 

@@ -172,6 +172,10 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
                            const int32_t *probe, int64_t nprobe, int64_t k, float *out_score, int64_t *out_id,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* Product-quantised lists ("IVF<n>,PQ<m>", "PQ<m>"): the ADC scan over byte codes, with its two sizing functions and the same
+ * workspace cap, declared and documented in mevi_hip_ivfpq.h. */
+#include "mevi_hip_ivfpq.h"
+
 /* IVF-Flat build, step 1: `index.train` / `index.add` label every row with its best centroid (faiss IndexIVFFlat with an
  * IndexFlatIP quantiser, MEVI/faiss_search.py:17-19) -- the nearest centroid by inner product, without the [n, nlist]
  * score matrix.

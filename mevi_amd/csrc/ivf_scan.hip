@@ -36,7 +36,7 @@
 
 #include "common.h"
 #include "mfma_pp.h"
-#include "select_topk.h"
+#include "ivf_select.h"
 
 namespace mevi {
 namespace {
@@ -44,8 +44,8 @@ namespace {
 constexpr int IVF_PAIR_TILE = MEVI_IVF_SCAN_PAIR_TILE;   // pairs (query, probe slot) of one list that share a pass over its rows
 constexpr int IVF_ROW_BLOCK = MEVI_IVF_SCAN_ROW_BLOCK;   // rows of a list per work item: 4 waves x 32
 constexpr int SCAN_THREADS = 256;
-constexpr int SEL_THREADS = 1024;
-constexpr int IVF_MAX_K = 4096;
+constexpr int SEL_THREADS = IVF_SEL_THREADS;
+constexpr int IVF_MAX_K = IVF_SEL_MAX_K;
 constexpr int IVF_MAX_NPROBE = 256;
 constexpr int64_t IVF_MAX_NLIST = 262144;
 constexpr int64_t IVF_MAX_QT = 4096;                      // queries per tile: 64 bitmap words per list
@@ -269,48 +269,14 @@ __global__ void __launch_bounds__(SCAN_THREADS) ivf_scan_kernel(const float *__r
 }
 
 // ---- selection --------------------------------------------------------------------------------------------------------
-// The selection itself (histogram, radix select, id pass at the cut, final sort) is select_topk.h.
+// The walk over a query's candidates is ivf_select.h (shared with ivfpq_scan.hip); the selection itself (histogram, radix
+// select, id pass at the cut, final sort) is select_topk.h.
 __global__ void __launch_bounds__(SEL_THREADS) ivf_select_kernel(const float *__restrict__ cand, long long ld,
                                                                  const int32_t *__restrict__ clean,
                                                                  const int64_t *__restrict__ off,
                                                                  const int64_t *__restrict__ row_ids, int nprobe, int k,
                                                                  int max_len, float *__restrict__ out_s, int64_t *__restrict__ out_i) {
-  __shared__ unsigned long long keys[IVF_MAX_K];
-  __shared__ int hist[2048];
-  const int q = blockIdx.x, t = threadIdx.x;
-  const int32_t *slots = clean + (size_t)q * nprobe;
-  const float *base = cand + (size_t)q * nprobe * (size_t)ld;
-
-  // f(score, list-major row) for every candidate of the query; four loads per thread are in flight before the first is used.
-  auto each = [&](auto f) {
-    for (int s = 0; s < nprobe; ++s) {
-      const int l = slots[s];
-      if (l < 0) continue;
-      const long long a = off[l];
-      const int len = (int)min((long long)max_len, off[l + 1] - a);
-      const float *p = base + (size_t)s * (size_t)ld;
-      for (int r0 = t; r0 < len; r0 += 4 * SEL_THREADS) {
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = r0 + u * SEL_THREADS < len ? p[r0 + u * SEL_THREADS] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (r0 + u * SEL_THREADS < len) f(v[u], (uint32_t)(a + r0 + u * SEL_THREADS));
-      }
-    }
-  };
-  auto id_of = [&](uint32_t row) { return row_ids ? (uint32_t)row_ids[row] : row; };
-  long long total = 0;
-  for (int s = 0; s < nprobe; ++s) {
-    const int l = slots[s];
-    if (l >= 0) total += max(0ll, min((long long)max_len, off[l + 1] - off[l]));
-  }
-  select_topk<SEL_THREADS>(each, id_of, total, k, keys, hist);
-  for (int i = t; i < k; i += SEL_THREADS) {
-    const unsigned long long key = keys[i];
-    out_s[(size_t)q * k + i] = key ? key_score(key) : -FLT_MAX;
-    out_i[(size_t)q * k + i] = key ? (int64_t)key_id(key) : -1;
-  }
+  ivf_select_body(cand, ld, clean, off, row_ids, nprobe, k, max_len, out_s, out_i);
 }
 
 }  // namespace

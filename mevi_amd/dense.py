@@ -223,6 +223,64 @@ def ivf_scan_topk(query, docs, list_offsets, row_ids, max_list_len, probe, k, ou
     return out_s, out_i
 
 
+IVFPQ_ROW_BLOCK = 1024              # MEVI_IVFPQ_SCAN_ROW_BLOCK: rows of a list per work item of the ADC scan
+IVFPQ_MAX_M = 96                    # subspaces (code bytes per row) the ADC scan takes; m % 4 == 0
+IVFPQ_MAX_LUT_BYTES = 96 << 10      # m * K * 4: one query's lookup table, kept in LDS by a scan workgroup
+
+
+def ivfpq_scan_workspace_bytes(nq, nprobe, k, dim, m, K, nlist, max_list_len):
+    """Bytes of workspace `ivfpq_scan_topk` needs (host arithmetic; 0 = shape outside the kernel's envelope); never above
+    IVF_WORKSPACE_CAP."""
+    return int(hip.lib().mevi_ivfpq_scan_workspace_bytes(nq, nprobe, k, dim, m, K, nlist, max_list_len))
+
+
+def ivfpq_scan_query_tile(nq, nprobe, k, dim, m, K, nlist, max_list_len):
+    """Queries per tile of `ivfpq_scan_topk` (0 = outside the envelope)."""
+    return int(hip.lib().mevi_ivfpq_scan_query_tile(nq, nprobe, k, dim, m, K, nlist, max_list_len))
+
+
+def ivfpq_scan_topk(query, codebook, codes, list_offsets, row_ids, max_list_len, probe, probe_score, k, out=None, workspace=None):
+    """Top-k of every query among the rows of the lists its probe row names, scored by ADC (mevi_ivfpq_scan_topk_f32).
+
+    query f32 [nq, dim]; codebook f32 [m, K, dim / m]; codes u8 [nd, m] list-major; list_offsets i64 [nlist + 1] on the device;
+    row_ids i64 [nd] or None (id = row); probe i32 [nq, nprobe] (entries outside [0, nlist) are empty, a repeated list counts
+    once, at its first slot); probe_score f32 [nq, nprobe] or None: the bias of every slot (None = +0).
+    score = ((bias + lut[0][code_0]) + lut[1][code_1]) + ..., lut[j][c] = the fmaf chain <q_j, codebook[j][c]>.
+    Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
+    `out` = (scores, ids) and `workspace` (uint8, ivfpq_scan_workspace_bytes) preallocated nothing is allocated either."""
+    hip.require_gpu()
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    assert codebook.is_cuda and codebook.dtype == torch.float32 and codebook.dim() == 3 and codebook.is_contiguous()
+    assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous() and codes.shape[1] == codebook.shape[0]
+    assert codebook.shape[0] * codebook.shape[2] == query.shape[1]
+    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
+    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
+    assert probe_score is None or (probe_score.is_cuda and probe_score.dtype == torch.float32 and probe_score.is_contiguous() and
+                                   probe_score.shape == probe.shape)
+    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == codes.shape[0])
+    nq, dim = query.shape
+    m, K = codebook.shape[0], codebook.shape[1]
+    nd, nlist, nprobe = codes.shape[0], list_offsets.numel() - 1, probe.shape[1]
+    L = hip.lib()
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
+    out_s, out_i = out
+    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    if nq == 0:
+        return out_s, out_i
+    if workspace is None:
+        workspace = torch.empty(L.mevi_ivfpq_scan_workspace_bytes(nq, nprobe, k, dim, m, K, nlist, max_list_len), dtype=torch.uint8,
+                                device=query.device)
+    with hip.device_guard(query.device):
+        st = L.mevi_ivfpq_scan_topk_f32(hip.ptr(query), nq, dim, hip.ptr(codebook), m, K, hip.ptr(codes) if nd else None,
+                                        hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids), nd, nlist, max_list_len,
+                                        hip.ptr(probe), None if probe_score is None else hip.ptr(probe_score), nprobe, k,
+                                        hip.ptr(out_s), hip.ptr(out_i), hip.ptr(workspace) if workspace.numel() else None,
+                                        workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_ivfpq_scan_topk_f32")
+    return out_s, out_i
+
+
 IVF_ASSIGN_ROWS = 256               # MEVI_IVF_ASSIGN_ROWS: rows a workgroup of `ivf_assign` keeps while it walks the centroids
 IVF_ASSIGN_COLS = 128               # MEVI_IVF_ASSIGN_COLS: centroids per tile of that walk (64 on grids too small for the device)
 IVF_ASSIGN_SPLIT_WGS = 256          # MEVI_IVF_ASSIGN_SPLIT_WGS: below this many row blocks the walk is split among workgroups
@@ -503,8 +561,11 @@ def search(query, doc, dim, topk, param="Flat", device=None):
 
     `param` is the faiss factory string the reference forwards: "Flat" -> exact search (result parity defined);
     "IVF<n>,Flat" (the script's default) -> IVF-Flat with faiss's structure and defaults (mevi_amd/ivf.py: inner-
-    product k-means, nprobe = MEVI_IVF_NPROBE or 1; recall vs the exact search is reported on stderr); every other
-    index type (HNSW*, PQ*, ...) is served by exact search (recall >= the approximate index it names).
+    product k-means, nprobe = MEVI_IVF_NPROBE or 1; recall vs the exact search is reported on stderr);
+    "IVF<n>,PQ<m>[x<b>]" / "PQ<m>[x<b>]" (b <= 8) -> product-quantised lists searched by ADC on the device
+    (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact answers them with the exact search instead, as do
+    shapes outside the index's envelope: dim % m != 0, m % 4 != 0, fewer rows than 2^b, nlist > rows, topk > 4096); every
+    other index type (HNSW*, OPQ*, SQ*, ...) is served by exact search (recall >= the approximate index it names).
     Returns numpy (dists f32[nq,topk], indices i64[nq,topk]).
     """
     hip.require_gpu()
@@ -512,11 +573,14 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     print(f"Param {param} trained: {is_trained_before_train(param)}.")  # index.is_trained before index.train
     q = _as_device_f32(np.asarray(query).reshape(-1, dim) if isinstance(query, np.ndarray) else query, device)
     d = _as_device_f32(np.asarray(doc).reshape(-1, dim) if isinstance(doc, np.ndarray) else doc, device)
-    from . import ivf
+    from . import ivf, ivfpq
 
     nlist = ivf.parse_factory(param)
+    pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     if nlist is not None and topk <= MAX_K and 0 < nlist <= d.shape[0]:
         s, i = ivf.search(q, d, topk, nlist)
+    elif pq is not None:
+        s, i = ivfpq.search(q, d, topk, *pq)
     elif topk > MAX_K:
         s, i = _search_large_k(q, d, topk)
     else:
@@ -531,7 +595,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
     Every search takes the batch from host memory and returns numpy arrays, like faiss's API.  Returns the `all_time` dict."""
     import time
 
-    from . import ivf
+    from . import ivf, ivfpq
 
     hip.require_gpu()
     device = torch.device(device if device is not None else "cuda")
@@ -547,12 +611,20 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         torch.cuda.synchronize()
         upload = time.time() - t
         use_ivf = nlist is not None and 0 < nlist <= d.shape[0] and topk <= MAX_K
+        pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         t = time.time()
         cent = ivf.train_centroids(d, nlist) if use_ivf else None      # index.train(doc)
+        if pq is not None:                                             # ... of the coarse and the product quantiser
+            cent = ivf.train_centroids(d, pq[0]) if pq[0] is not None else None
+            book = ivfpq.train_codebook(d, ivf.assign(d, cent) if cent is not None else None, cent, pq[1], pq[2])
         torch.cuda.synchronize()
         all_time["train"] += time.time() - t
         t = time.time()
-        index = ivf.IVFFlatIndex(d, nlist, centroids=cent) if use_ivf else (DenseIndex(d) if topk <= MAX_K else None)
+        if pq is not None:                                             # index.add(doc): lists and codes
+            index = ivfpq.IVFPQIndex(d, pq[0], pq[1], pq[2], centroids=cent, codebook=book)
+            use_ivf = True
+        else:
+            index = ivf.IVFFlatIndex(d, nlist, centroids=cent) if use_ivf else (DenseIndex(d) if topk <= MAX_K else None)
         if isinstance(index, DenseIndex) and any(index.small_image_wanted(b, topk) for b in bs):
             index.prepare_small()                               # the 8-bit image of the small batches is part of index.add
         torch.cuda.synchronize()

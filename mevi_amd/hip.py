@@ -197,6 +197,16 @@ _FINE_AGG_SIGNATURES = {
 }
 
 
+# include/mevi_hip_ivfpq.h (included by mevi_hip.h): the ADC scan of product-quantised lists
+_IVFPQ_SIGNATURES = {
+    "mevi_ivfpq_scan_workspace_bytes": (c_size_t, [c_int64] * 8),
+    "mevi_ivfpq_scan_query_tile": (c_int64, [c_int64] * 8),
+    "mevi_ivfpq_scan_topk_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
+}
+
+
 # include/mevi_hip_attn_long.h (included by mevi_hip.h): attention over up to ATTN_LONG_MAX_KEYS keys
 _ATTN_LONG_SIGNATURES = {
     "mevi_attention_long_f32": _SIGNATURES["mevi_attention_f32"],
@@ -227,10 +237,10 @@ def attn_route_name(route):
 
 
 def exported_symbols(header="mevi_hip.h"):
-    """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h,
-    which it includes)."""
+    """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h /
+    mevi_hip_ivfpq.h, which it includes)."""
     return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES,
-                   "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES}[header])
+                   "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES}[header])
 
 
 def lib():
@@ -241,7 +251,7 @@ def lib():
                 f"{LIB} not found: build it with `python -m mevi_amd.build` "
                 "(or __graft_entry__.build()); mevi_amd has no CPU fallback")
         L = ctypes.CDLL(LIB)
-        for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

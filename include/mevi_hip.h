@@ -176,6 +176,10 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
  * workspace cap, declared and documented in mevi_hip_ivfpq.h. */
 #include "mevi_hip_ivfpq.h"
 
+/* A neighbour graph over the rows ("HNSW<M>"): linking it from exact kNN lists and the best-first search over it, declared and
+ * documented in mevi_hip_graph.h. */
+#include "mevi_hip_graph.h"
+
 /* IVF-Flat build, step 1: `index.train` / `index.add` label every row with its best centroid (faiss IndexIVFFlat with an
  * IndexFlatIP quantiser, MEVI/faiss_search.py:17-19) -- the nearest centroid by inner product, without the [n, nlist]
  * score matrix.

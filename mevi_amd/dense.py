@@ -281,6 +281,81 @@ def ivfpq_scan_topk(query, codebook, codes, list_offsets, row_ids, max_list_len,
     return out_s, out_i
 
 
+GRAPH_MAX_EF = 4096                 # MEVI_GRAPH_MAX_EF: entries of a walk's candidate list
+GRAPH_MAX_BATCH = 2048              # MEVI_GRAPH_MAX_BATCH: width * degree, the ids one step of a walk reads
+GRAPH_LINK_MIN_ROWS = 4096          # MEVI_GRAPH_LINK_MIN_ROWS: destination rows the smallest link workspace holds
+
+
+def graph_link_workspace_bytes(nd, C, M):
+    """Bytes of the smallest workspace `graph_link` takes (host arithmetic; 0 = outside the envelope)."""
+    return int(hip.lib().mevi_graph_link_workspace_bytes(nd, C, M))
+
+
+def graph_link(knn, M, workspace=None):
+    """graph i32 [nd, 2 * M] from knn i64 [nd, C] (mevi_graph_link, include/mevi_hip_graph.h): the first M distinct valid others
+    of every list, then the reverse links in ascending (rank, source) order, -1 padding.  Any workspace of at least
+    graph_link_workspace_bytes gives the same graph; a larger one walks the destination rows in fewer ranges."""
+    hip.require_gpu()
+    assert knn.is_cuda and knn.dtype == torch.int64 and knn.dim() == 2 and knn.is_contiguous()
+    nd, C = knn.shape
+    graph = torch.empty((nd, 2 * M), dtype=torch.int32, device=knn.device)
+    if nd == 0:
+        return graph
+    L = hip.lib()
+    if workspace is None:
+        need = L.mevi_graph_link_workspace_bytes(nd, C, M)
+        workspace = torch.empty(max(need, min(nd * 2 * M * 8, 1 << 30)) if need else 0, dtype=torch.uint8, device=knn.device)
+    with hip.device_guard(knn.device):
+        st = L.mevi_graph_link(hip.ptr(knn), nd, C, M, hip.ptr(graph), hip.ptr(workspace) if workspace.numel() else None,
+                               workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_graph_link")
+    return graph
+
+
+def graph_search_workspace_bytes(nq, dim, degree, nseed, k, ef, width, max_steps):
+    """Bytes of workspace `graph_search_topk` needs (host arithmetic; 0 = outside the kernel's envelope)."""
+    return int(hip.lib().mevi_graph_search_workspace_bytes(nq, dim, degree, nseed, k, ef, width, max_steps))
+
+
+def graph_search_topk(query, docs, graph, seed, seed_score, k, ef, width=1, max_steps=None, out=None, workspace=None, steps=None):
+    """Best-first search over a neighbour graph (mevi_graph_search_topk_f32, include/mevi_hip_graph.h).
+
+    query f32 [nq, dim]; docs f32 [nd, dim]; graph i32 [nd, degree]; seed i32 [nq, nseed]; seed_score f32 [nq, nseed] or None
+    (the seeds are scored); a candidate list of `ef` entries, `width` entries expanded per step, at most `max_steps` steps
+    (default 4 * ef).  `steps` i32 [nq] or None receives the steps taken.  Returns (scores f32 [nq, k] desc, ids i64 [nq, k];
+    ties by ascending id; -FLT_MAX / -1 padding).  After the call the first nq u32 of `workspace` hold the rows every walk scored.
+    Stream-ordered: with `out` and `workspace` (uint8, graph_search_workspace_bytes) preallocated nothing is allocated either."""
+    hip.require_gpu()
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2 and docs.is_contiguous() and docs.shape[1] == query.shape[1]
+    assert graph.is_cuda and graph.dtype == torch.int32 and graph.dim() == 2 and graph.is_contiguous() and graph.shape[0] == docs.shape[0]
+    assert seed.is_cuda and seed.dtype == torch.int32 and seed.dim() == 2 and seed.is_contiguous() and seed.shape[0] == query.shape[0]
+    assert seed_score is None or (seed_score.is_cuda and seed_score.dtype == torch.float32 and seed_score.is_contiguous() and
+                                  seed_score.shape == seed.shape)
+    assert steps is None or (steps.is_cuda and steps.dtype == torch.int32 and steps.is_contiguous() and steps.numel() == query.shape[0])
+    nq, dim = query.shape
+    nd, degree, nseed = docs.shape[0], graph.shape[1], seed.shape[1]
+    if max_steps is None:
+        max_steps = 4 * ef
+    L = hip.lib()
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
+    out_s, out_i = out
+    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    if nq == 0:
+        return out_s, out_i
+    if workspace is None:
+        workspace = torch.empty(L.mevi_graph_search_workspace_bytes(nq, dim, degree, nseed, k, ef, width, max_steps), dtype=torch.uint8,
+                                device=query.device)
+    with hip.device_guard(query.device):
+        st = L.mevi_graph_search_topk_f32(hip.ptr(query), nq, dim, hip.ptr(docs) if nd else None, nd, hip.ptr(graph) if nd else None,
+                                          degree, hip.ptr(seed), None if seed_score is None else hip.ptr(seed_score), nseed, k, ef,
+                                          width, max_steps, hip.ptr(out_s), hip.ptr(out_i), None if steps is None else hip.ptr(steps),
+                                          hip.ptr(workspace) if workspace.numel() else None, workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_graph_search_topk_f32")
+    return out_s, out_i
+
+
 IVF_ASSIGN_ROWS = 256               # MEVI_IVF_ASSIGN_ROWS: rows a workgroup of `ivf_assign` keeps while it walks the centroids
 IVF_ASSIGN_COLS = 128               # MEVI_IVF_ASSIGN_COLS: centroids per tile of that walk (64 on grids too small for the device)
 IVF_ASSIGN_SPLIT_WGS = 256          # MEVI_IVF_ASSIGN_SPLIT_WGS: below this many row blocks the walk is split among workgroups
@@ -564,8 +639,12 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     product k-means, nprobe = MEVI_IVF_NPROBE or 1; recall vs the exact search is reported on stderr);
     "IVF<n>,PQ<m>[x<b>]" / "PQ<m>[x<b>]" (b <= 8) -> product-quantised lists searched by ADC on the device
     (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact answers them with the exact search instead, as do
-    shapes outside the index's envelope: dim % m != 0, m % 4 != 0, fewer rows than 2^b, nlist > rows, topk > 4096); every
-    other index type (HNSW*, OPQ*, SQ*, ...) is served by exact search (recall >= the approximate index it names).
+    shapes outside the index's envelope: dim % m != 0, m % 4 != 0, fewer rows than 2^b, nlist > rows, topk > 4096);
+    "HNSW<M>" / "HNSW<M>,Flat" -> a neighbour graph of degree 2M walked on the device (mevi_amd/hnsw.py: exact kNN links plus
+    reverse links, no pruning, no upper levels; efSearch = MEVI_HNSW_EFSEARCH or 16; recall and steps on stderr;
+    MEVI_HNSW=exact answers it with the exact search instead, as do dim % 4 != 0, M outside 2..256, topk > 4096 and corpora
+    of fewer than 64 * 2M rows, where a graph of that degree is close to complete); every other index type (HNSW<M>_PQ*,
+    OPQ*, SQ*, ...) is served by exact search (recall >= the approximate index it names).
     Returns numpy (dists f32[nq,topk], indices i64[nq,topk]).
     """
     hip.require_gpu()
@@ -573,14 +652,17 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     print(f"Param {param} trained: {is_trained_before_train(param)}.")  # index.is_trained before index.train
     q = _as_device_f32(np.asarray(query).reshape(-1, dim) if isinstance(query, np.ndarray) else query, device)
     d = _as_device_f32(np.asarray(doc).reshape(-1, dim) if isinstance(doc, np.ndarray) else doc, device)
-    from . import ivf, ivfpq
+    from . import hnsw, ivf, ivfpq
 
     nlist = ivf.parse_factory(param)
     pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+    links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
     if nlist is not None and topk <= MAX_K and 0 < nlist <= d.shape[0]:
         s, i = ivf.search(q, d, topk, nlist)
     elif pq is not None:
         s, i = ivfpq.search(q, d, topk, *pq)
+    elif links is not None:
+        s, i = hnsw.search(q, d, topk, links)
     elif topk > MAX_K:
         s, i = _search_large_k(q, d, topk)
     else:
@@ -595,7 +677,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
     Every search takes the batch from host memory and returns numpy arrays, like faiss's API.  Returns the `all_time` dict."""
     import time
 
-    from . import ivf, ivfpq
+    from . import hnsw, ivf, ivfpq
 
     hip.require_gpu()
     device = torch.device(device if device is not None else "cuda")
@@ -620,9 +702,12 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         torch.cuda.synchronize()
         all_time["train"] += time.time() - t
         t = time.time()
+        links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
         if pq is not None:                                             # index.add(doc): lists and codes
             index = ivfpq.IVFPQIndex(d, pq[0], pq[1], pq[2], centroids=cent, codebook=book)
             use_ivf = True
+        elif links is not None and not use_ivf:                        # index.add(doc): kNN lists, links, entry rows
+            index = hnsw.HNSWIndex(d, links)
         else:
             index = ivf.IVFFlatIndex(d, nlist, centroids=cent) if use_ivf else (DenseIndex(d) if topk <= MAX_K else None)
         if isinstance(index, DenseIndex) and any(index.small_image_wanted(b, topk) for b in bs):
@@ -634,6 +719,8 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
             q = torch.from_numpy(np.ascontiguousarray(bq)).to(device)
             if use_ivf:
                 s, i = index.search(q, topk, int(os.environ.get("MEVI_IVF_NPROBE", "1")))
+            elif links is not None:
+                s, i = index.search(q, topk)
             elif index is None:
                 s, i = _search_large_k(q, d, topk)
             else:

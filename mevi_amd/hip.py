@@ -207,6 +207,17 @@ _IVFPQ_SIGNATURES = {
 }
 
 
+# include/mevi_hip_graph.h (included by mevi_hip.h): the neighbour graph of "HNSW<M>", its linking and its search
+_GRAPH_SIGNATURES = {
+    "mevi_graph_link_workspace_bytes": (c_size_t, [c_int64] * 3),
+    "mevi_graph_link": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mevi_graph_search_workspace_bytes": (c_size_t, [c_int64] * 8),
+    "mevi_graph_search_topk_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                           c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
+}
+
+
 # include/mevi_hip_attn_long.h (included by mevi_hip.h): attention over up to ATTN_LONG_MAX_KEYS keys
 _ATTN_LONG_SIGNATURES = {
     "mevi_attention_long_f32": _SIGNATURES["mevi_attention_f32"],
@@ -238,9 +249,10 @@ def attn_route_name(route):
 
 def exported_symbols(header="mevi_hip.h"):
     """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h /
-    mevi_hip_ivfpq.h, which it includes)."""
+    mevi_hip_ivfpq.h / mevi_hip_graph.h, which it includes)."""
     return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES,
-                   "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES}[header])
+                   "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES,
+                   "mevi_hip_graph.h": _GRAPH_SIGNATURES}[header])
 
 
 def lib():
@@ -251,7 +263,8 @@ def lib():
                 f"{LIB} not found: build it with `python -m mevi_amd.build` "
                 "(or __graft_entry__.build()); mevi_amd has no CPU fallback")
         L = ctypes.CDLL(LIB)
-        for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES,
+                                  **_GRAPH_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

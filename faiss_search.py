@@ -6,7 +6,10 @@ MEVI/faiss_search.py:80-98, served by the MI355X inner-product top-k instead of 
 builds an IVF-Flat index with faiss's structure and defaults (mevi_amd/ivf.py; nprobe from MEVI_IVF_NPROBE, default 1)
 and reports its recall against the exact search on stderr; "IVF<n>,PQ<m>[x<b>]" and "PQ<m>[x<b>]" (b <= 8) build
 product-quantised lists searched by ADC on the device (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact or a
-shape outside the index's envelope gives the exact search instead); any other index type is answered with EXACT search.
+shape outside the index's envelope gives the exact search instead); "HNSW<M>" builds a neighbour graph walked on the device
+(mevi_amd/hnsw.py; efSearch from MEVI_HNSW_EFSEARCH, default 16; MEVI_HNSW_ENTRY=levels seeds the walk by descending
+deterministic upper levels instead of scanning strided entry rows; MEVI_HNSW=exact gives the exact search instead); any other
+index type is answered with EXACT search.
 With torch.distributed initialised (torchrun) the corpus file is row-sharded across ranks and searched exactly.
 """
 import argparse

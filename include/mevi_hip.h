@@ -180,6 +180,10 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
  * documented in mevi_hip_graph.h. */
 #include "mevi_hip_graph.h"
 
+/* The upper levels of that index (opt-in): one call that descends a hierarchy of such graphs from an exhaustively scanned top
+ * level to the seeds of the level-0 search, declared and documented in mevi_hip_graph_levels.h. */
+#include "mevi_hip_graph_levels.h"
+
 /* IVF-Flat build, step 1: `index.train` / `index.add` label every row with its best centroid (faiss IndexIVFFlat with an
  * IndexFlatIP quantiser, MEVI/faiss_search.py:17-19) -- the nearest centroid by inner product, without the [n, nlist]
  * score matrix.

@@ -356,6 +356,69 @@ def graph_search_topk(query, docs, graph, seed, seed_score, k, ef, width=1, max_
     return out_s, out_i
 
 
+GRAPH_MAX_LEVELS = 8                # MEVI_GRAPH_MAX_LEVELS: walked upper levels of one descent
+GRAPH_DESCEND_MAX_EF = 256          # MEVI_GRAPH_DESCEND_MAX_EF: entries of the descent's candidate list
+
+
+def graph_descend_workspace_bytes(nq, dim, degree, n_levels, nseed_in, nseed_out, ef, width, max_steps):
+    """Bytes of workspace `graph_descend` needs (host arithmetic; 0 = outside the kernel's envelope)."""
+    return int(hip.lib().mevi_graph_descend_workspace_bytes(nq, dim, degree, n_levels, nseed_in, nseed_out, ef, width, max_steps))
+
+
+def graph_descend(query, docs, graphs, rows, down, level_n, seed, seed_score, ef, width=1, max_steps=None, nseed_out=None, out=None,
+                  workspace=None, steps=None):
+    """The descent through the upper levels of a neighbour-graph index (mevi_graph_descend_f32, include/mevi_hip_graph_levels.h).
+
+    query f32 [nq, dim]; docs f32 [nd, dim]; graphs i32 [sum n_l, degree], rows i32 [sum n_l], down i32 [sum n_l]: the walked
+    levels concatenated, level 1 first, local ids; level_n: their sizes, a sequence of ints on the host; seed i64 [nq, nseed_in]
+    local ids of the last level with seed_score f32, as `ivf_scan_topk` returns them.  Per level a walk with a list of `ef`
+    entries, `width` entries expanded per step and at most `max_steps` steps (default 4 * ef); the best `nseed_out` (default
+    min(ef, 32)) entries go one level down.  Returns (seed i32 [nq, nseed_out], score f32 [nq, nseed_out]): the `seed` and
+    `seed_score` of `graph_search_topk`, -1 / -FLT_MAX padding.  `steps` i32 [nq] or None receives the steps of all levels; after
+    the call the first nq u32 of `workspace` hold the rows every descent scored.  Stream-ordered: with `out` and `workspace`
+    (uint8, graph_descend_workspace_bytes) preallocated nothing is allocated either."""
+    import ctypes
+
+    hip.require_gpu()
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2 and docs.is_contiguous() and docs.shape[1] == query.shape[1]
+    level_n = [int(n) for n in level_n]
+    total = sum(level_n)
+    assert graphs.is_cuda and graphs.dtype == torch.int32 and graphs.dim() == 2 and graphs.is_contiguous() and graphs.shape[0] == total
+    for m in (rows, down):
+        assert m.is_cuda and m.dtype == torch.int32 and m.dim() == 1 and m.is_contiguous() and m.numel() == total
+    assert seed.is_cuda and seed.dtype == torch.int64 and seed.dim() == 2 and seed.is_contiguous() and seed.shape[0] == query.shape[0]
+    assert seed_score.is_cuda and seed_score.dtype == torch.float32 and seed_score.is_contiguous() and seed_score.shape == seed.shape
+    assert steps is None or (steps.is_cuda and steps.dtype == torch.int32 and steps.is_contiguous() and steps.numel() == query.shape[0])
+    nq, dim = query.shape
+    nd, degree, nseed_in = docs.shape[0], graphs.shape[1], seed.shape[1]
+    if max_steps is None:
+        max_steps = 4 * ef
+    if nseed_out is None:
+        nseed_out = min(ef, 32)
+    L = hip.lib()
+    if out is None:
+        out = (torch.empty((nq, nseed_out), dtype=torch.int32, device=query.device),
+               torch.empty((nq, nseed_out), dtype=torch.float32, device=query.device))
+    out_i, out_s = out
+    assert out_i.shape == (nq, nseed_out) and out_s.shape == (nq, nseed_out) and out_i.is_contiguous() and out_s.is_contiguous()
+    assert out_i.dtype == torch.int32 and out_s.dtype == torch.float32
+    if nq == 0:
+        return out_i, out_s
+    if workspace is None:
+        workspace = torch.empty(L.mevi_graph_descend_workspace_bytes(nq, dim, degree, len(level_n), nseed_in, nseed_out, ef, width, max_steps),
+                                dtype=torch.uint8, device=query.device)
+    sizes = (ctypes.c_int64 * max(1, len(level_n)))(*level_n)               # read by the call before it launches
+    with hip.device_guard(query.device):
+        st = L.mevi_graph_descend_f32(hip.ptr(query), nq, dim, hip.ptr(docs) if nd else None, nd, hip.ptr(graphs), degree, hip.ptr(rows),
+                                      hip.ptr(down), ctypes.addressof(sizes), len(level_n), hip.ptr(seed), hip.ptr(seed_score), nseed_in,
+                                      ef, width, max_steps, nseed_out, hip.ptr(out_i), hip.ptr(out_s),
+                                      None if steps is None else hip.ptr(steps), hip.ptr(workspace) if workspace.numel() else None,
+                                      workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_graph_descend_f32")
+    return out_i, out_s
+
+
 IVF_ASSIGN_ROWS = 256               # MEVI_IVF_ASSIGN_ROWS: rows a workgroup of `ivf_assign` keeps while it walks the centroids
 IVF_ASSIGN_COLS = 128               # MEVI_IVF_ASSIGN_COLS: centroids per tile of that walk (64 on grids too small for the device)
 IVF_ASSIGN_SPLIT_WGS = 256          # MEVI_IVF_ASSIGN_SPLIT_WGS: below this many row blocks the walk is split among workgroups
@@ -641,7 +704,8 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact answers them with the exact search instead, as do
     shapes outside the index's envelope: dim % m != 0, m % 4 != 0, fewer rows than 2^b, nlist > rows, topk > 4096);
     "HNSW<M>" / "HNSW<M>,Flat" -> a neighbour graph of degree 2M walked on the device (mevi_amd/hnsw.py: exact kNN links plus
-    reverse links, no pruning, no upper levels; efSearch = MEVI_HNSW_EFSEARCH or 16; recall and steps on stderr;
+    reverse links, no pruning; seeds from strided entry rows or, with MEVI_HNSW_ENTRY=levels, from a descent through
+    deterministic upper levels; efSearch = MEVI_HNSW_EFSEARCH or 16; recall and steps on stderr;
     MEVI_HNSW=exact answers it with the exact search instead, as do dim % 4 != 0, M outside 2..256, topk > 4096 and corpora
     of fewer than 64 * 2M rows, where a graph of that degree is close to complete); every other index type (HNSW<M>_PQ*,
     OPQ*, SQ*, ...) is served by exact search (recall >= the approximate index it names).

@@ -218,6 +218,15 @@ _GRAPH_SIGNATURES = {
 }
 
 
+# include/mevi_hip_graph_levels.h (included by mevi_hip.h): the descent through the upper levels of that index
+_GRAPH_LEVELS_SIGNATURES = {
+    "mevi_graph_descend_workspace_bytes": (c_size_t, [c_int64] * 9),
+    "mevi_graph_descend_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
+
 # include/mevi_hip_attn_long.h (included by mevi_hip.h): attention over up to ATTN_LONG_MAX_KEYS keys
 _ATTN_LONG_SIGNATURES = {
     "mevi_attention_long_f32": _SIGNATURES["mevi_attention_f32"],
@@ -249,10 +258,10 @@ def attn_route_name(route):
 
 def exported_symbols(header="mevi_hip.h"):
     """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h /
-    mevi_hip_ivfpq.h / mevi_hip_graph.h, which it includes)."""
+    mevi_hip_ivfpq.h / mevi_hip_graph.h / mevi_hip_graph_levels.h, which it includes)."""
     return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES,
                    "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES,
-                   "mevi_hip_graph.h": _GRAPH_SIGNATURES}[header])
+                   "mevi_hip_graph.h": _GRAPH_SIGNATURES, "mevi_hip_graph_levels.h": _GRAPH_LEVELS_SIGNATURES}[header])
 
 
 def lib():
@@ -264,7 +273,7 @@ def lib():
                 "(or __graft_entry__.build()); mevi_amd has no CPU fallback")
         L = ctypes.CDLL(LIB)
         for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES,
-                                  **_GRAPH_SIGNATURES}.items():
+                                  **_GRAPH_SIGNATURES, **_GRAPH_LEVELS_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -8,8 +8,10 @@ and reports its recall against the exact search on stderr; "IVF<n>,PQ<m>[x<b>]" 
 product-quantised lists searched by ADC on the device (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact or a
 shape outside the index's envelope gives the exact search instead); "HNSW<M>" builds a neighbour graph walked on the device
 (mevi_amd/hnsw.py; efSearch from MEVI_HNSW_EFSEARCH, default 16; MEVI_HNSW_ENTRY=levels seeds the walk by descending
-deterministic upper levels instead of scanning strided entry rows; MEVI_HNSW=exact gives the exact search instead); any other
-index type is answered with EXACT search.
+deterministic upper levels instead of scanning strided entry rows; MEVI_HNSW=exact gives the exact search instead); "SQ8", "SQ4",
+"IVF<n>,SQ8" and "IVF<n>,SQ4" build scalar-quantised rows (one byte or one nibble per dimension) decoded inside the list scan on
+the device (mevi_amd/sq.py; same nprobe and recall report; MEVI_SQ=exact or a shape outside the index's envelope gives the exact
+search instead); any other index type is answered with EXACT search.
 With torch.distributed initialised (torchrun) the corpus file is row-sharded across ranks and searched exactly.
 """
 import argparse

@@ -176,6 +176,11 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
  * workspace cap, declared and documented in mevi_hip_ivfpq.h. */
 #include "mevi_hip_ivfpq.h"
 
+/* Scalar-quantised rows ("SQ8", "SQ4", "IVF<n>,SQ8", "IVF<n>,SQ4"): the encoder and the list scan that decodes one byte or one
+ * nibble per dimension in registers, with the sizing functions and the workspace cap of the scan above, declared and documented in
+ * mevi_hip_sq.h. */
+#include "mevi_hip_sq.h"
+
 /* A neighbour graph over the rows ("HNSW<M>"): linking it from exact kNN lists and the best-first search over it, declared and
  * documented in mevi_hip_graph.h. */
 #include "mevi_hip_graph.h"

@@ -36,6 +36,7 @@
 
 #include "common.h"
 #include "mfma_pp.h"
+#include "ivf_group.h"
 #include "ivf_select.h"
 
 namespace mevi {
@@ -52,14 +53,9 @@ constexpr int64_t IVF_MAX_QT = 4096;                      // queries per tile: 6
 constexpr size_t IVF_CAND_CAP = (size_t)2 << 30;
 static_assert(IVF_PAIR_TILE == 64 && IVF_ROW_BLOCK == 128, "the scan kernel's wave layout is 4 x (32 rows x 64 pairs)");
 
-struct IvfPlan {
-  int64_t qt;        // queries per tile
-  int64_t words;     // bitmap words per list
-  int64_t ld;        // candidate row stride (floats)
-  size_t cand, clean, pair_q, pair_slot, bits, pair_off, item_off, total;   // byte offsets, total size
-};
+}  // namespace
 
-// Host arithmetic only.  False: outside the envelope.
+// Host arithmetic only.  False: outside the envelope.  (IvfPlan: ivf_group.h; sq_scan.hip plans with it too.)
 bool ivf_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t dim, int64_t nlist, int64_t max_list_len, IvfPlan &p) {
   if (nq < 1 || nprobe < 1 || nprobe > IVF_MAX_NPROBE || k < 1 || k > IVF_MAX_K || dim < 4 || dim % 4 != 0 || nlist < 1 ||
       nlist > IVF_MAX_NLIST || max_list_len < 0 || max_list_len > 0x7fffffff)
@@ -89,6 +85,8 @@ bool ivf_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t dim, int64_t nlist,
   p.total = o;
   return true;
 }
+
+namespace {
 
 // ---- grouping ---------------------------------------------------------------------------------------------------------
 // One thread per (query of the tile, slot): the slot survives when its list exists and no earlier slot of the row names it.
@@ -168,6 +166,26 @@ __global__ void ivf_scatter_kernel(const int32_t *__restrict__ clean, int qn, in
   pair_q[pos] = q;
   pair_slot[pos] = s;
 }
+
+}  // namespace
+
+hipError_t ivf_group_tile(const IvfPlan &p, char *ws, const int32_t *probe, const int64_t *list_offsets, int qn, int nprobe,
+                          int nlist, int max_list_len, hipStream_t st) {
+  int32_t *clean = (int32_t *)(ws + p.clean), *pair_q = (int32_t *)(ws + p.pair_q), *pair_slot = (int32_t *)(ws + p.pair_slot);
+  unsigned long long *bits = (unsigned long long *)(ws + p.bits);
+  int32_t *pair_off = (int32_t *)(ws + p.pair_off), *item_off = (int32_t *)(ws + p.item_off);
+  const int npairs = qn * nprobe;
+  const int words = (qn + 63) / 64;                    // this tile's row width (<= p.words)
+  const hipError_t e = hipMemsetAsync(bits, 0, (size_t)nlist * words * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return e;
+  const int pair_blocks = (npairs + 255) / 256;
+  ivf_mark_kernel<<<pair_blocks, 256, 0, st>>>(probe, qn, nprobe, nlist, words, clean, bits);
+  ivf_plan_kernel<<<1, 1024, 0, st>>>(bits, list_offsets, nlist, words, max_list_len, pair_off, item_off);
+  ivf_scatter_kernel<<<pair_blocks, 256, 0, st>>>(clean, qn, nprobe, words, bits, pair_off, pair_q, pair_slot);
+  return hipSuccess;
+}
+
+namespace {
 
 // ---- scan -------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(SCAN_THREADS) ivf_scan_kernel(const float *__restrict__ query, const float *__restrict__ docs,
@@ -329,18 +347,12 @@ extern "C" int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *d
   char *ws = (char *)workspace;
   float *cand = (float *)(ws + p.cand);
   int32_t *clean = (int32_t *)(ws + p.clean), *pair_q = (int32_t *)(ws + p.pair_q), *pair_slot = (int32_t *)(ws + p.pair_slot);
-  unsigned long long *bits = (unsigned long long *)(ws + p.bits);
   int32_t *pair_off = (int32_t *)(ws + p.pair_off), *item_off = (int32_t *)(ws + p.item_off);
   const int64_t row_blocks = (max_list_len + IVF_ROW_BLOCK - 1) / IVF_ROW_BLOCK;
   for (int64_t q0 = 0; q0 < nq; q0 += p.qt) {
     const int qn = (int)(nq - q0 < p.qt ? nq - q0 : p.qt);
     const int npairs = qn * (int)nprobe;
-    const int words = (qn + 63) / 64;                  // this tile's row width (<= p.words)
-    MEVI_HIP_CHECK(hipMemsetAsync(bits, 0, (size_t)nlist * words * sizeof(unsigned long long), st));
-    const int pair_blocks = (npairs + 255) / 256;
-    ivf_mark_kernel<<<pair_blocks, 256, 0, st>>>(probe + q0 * nprobe, qn, (int)nprobe, (int)nlist, words, clean, bits);
-    ivf_plan_kernel<<<1, 1024, 0, st>>>(bits, list_offsets, (int)nlist, words, (int)max_list_len, pair_off, item_off);
-    ivf_scatter_kernel<<<pair_blocks, 256, 0, st>>>(clean, qn, (int)nprobe, words, bits, pair_off, pair_q, pair_slot);
+    MEVI_HIP_CHECK(ivf_group_tile(p, ws, probe + q0 * nprobe, list_offsets, qn, (int)nprobe, (int)nlist, (int)max_list_len, st));
     // at most one item per (pair, row block); beyond three workgroups per CU (what the kernel's registers leave resident:
     // one round of workgroups, each with an equal share of the items) the persistent loop takes the rest
     int64_t grid = (int64_t)npairs * (row_blocks > 0 ? row_blocks : 1);

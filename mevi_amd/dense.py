@@ -281,6 +281,92 @@ def ivfpq_scan_topk(query, codebook, codes, list_offsets, row_ids, max_list_len,
     return out_s, out_i
 
 
+SQ_MAX_DIM = 4096                   # columns a scalar-quantised row may have (include/mevi_hip_sq.h)
+
+
+def sq_scan_workspace_bytes(nq, nprobe, k, dim, bits, nlist, max_list_len):
+    """Bytes of workspace `sq_scan_topk` needs (host arithmetic; 0 = shape outside the kernel's envelope); never above
+    IVF_WORKSPACE_CAP."""
+    return int(hip.lib().mevi_sq_scan_workspace_bytes(nq, nprobe, k, dim, bits, nlist, max_list_len))
+
+
+def sq_scan_query_tile(nq, nprobe, k, dim, bits, nlist, max_list_len):
+    """Queries per tile of `sq_scan_topk` (0 = outside the envelope)."""
+    return int(hip.lib().mevi_sq_scan_query_tile(nq, nprobe, k, dim, bits, nlist, max_list_len))
+
+
+def sq_encode(x, rows, list_of, centroids, vmin, vdiff, bits, out=None):
+    """u8 [n, dim * bits / 8]: the scalar-quantised codes of x[rows] (rows None: of x) in that order (mevi_sq_encode_f32).
+
+    x f32 [n_src, dim]; rows i64 [n] or None; list_of i32 [n_src] + centroids f32 [nlist, dim] (the residual x - centroid[list of
+    the source row] is what is coded) or both None; vmin, vdiff f32 [dim]; bits 4 or 8.  One pass, stream-ordered."""
+    hip.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    assert rows is None or (rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous())
+    assert (list_of is None) == (centroids is None)
+    if centroids is not None:
+        assert list_of.is_cuda and list_of.dtype == torch.int32 and list_of.is_contiguous() and list_of.numel() == x.shape[0]
+        assert centroids.is_cuda and centroids.dtype == torch.float32 and centroids.is_contiguous() and centroids.shape[1] == x.shape[1]
+    for v in (vmin, vdiff):
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (x.shape[1],)
+    n_src, dim = x.shape
+    n = n_src if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty((n, dim * bits // 8), dtype=torch.uint8, device=x.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (n, dim * bits // 8)
+    with hip.device_guard(x.device):
+        st = hip.lib().mevi_sq_encode_f32(hip.ptr(x) if n_src else None, n_src, dim, None if rows is None else hip.ptr(rows), n,
+                                          None if list_of is None else hip.ptr(list_of),
+                                          None if centroids is None else hip.ptr(centroids), 0 if centroids is None else centroids.shape[0],
+                                          hip.ptr(vmin), hip.ptr(vdiff), bits, hip.ptr(out) if n else None, hip.stream_ptr())
+    hip.check(st, "mevi_sq_encode_f32")
+    return out
+
+
+def sq_scan_topk(query, codes, vmin, vdiff, bits, list_offsets, row_ids, max_list_len, probe, probe_score, k, out=None, workspace=None):
+    """Top-k of every query among the rows of the lists its probe row names, every row decoded from its scalar-quantised codes
+    (mevi_sq_scan_topk_f32).
+
+    query f32 [nq, dim]; codes u8 [nd, dim * bits / 8] list-major; vmin, vdiff f32 [dim]; bits 4 or 8; list_offsets i64 [nlist + 1]
+    on the device; row_ids i64 [nd] or None (id = row); probe i32 [nq, nprobe] (entries outside [0, nlist) are empty, a repeated
+    list counts once, at its first slot); probe_score f32 [nq, nprobe] or None: the bias of every slot (None: no addition).
+    score = the fmaf chain <q, vmin + vdiff * T[code]> (+ bias): the bits `ivf_scan_topk` gives over the decoded rows.
+    Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
+    `out` = (scores, ids) and `workspace` (uint8, sq_scan_workspace_bytes) preallocated nothing is allocated either."""
+    hip.require_gpu()
+    assert bits in (4, 8)
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous()
+    assert codes.shape[1] * 8 == query.shape[1] * bits
+    for v in (vmin, vdiff):
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (query.shape[1],)
+    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
+    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
+    assert probe_score is None or (probe_score.is_cuda and probe_score.dtype == torch.float32 and probe_score.is_contiguous() and
+                                   probe_score.shape == probe.shape)
+    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == codes.shape[0])
+    nq, dim = query.shape
+    nd, nlist, nprobe = codes.shape[0], list_offsets.numel() - 1, probe.shape[1]
+    L = hip.lib()
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
+    out_s, out_i = out
+    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    if nq == 0:
+        return out_s, out_i
+    if workspace is None:
+        workspace = torch.empty(L.mevi_sq_scan_workspace_bytes(nq, nprobe, k, dim, bits, nlist, max_list_len), dtype=torch.uint8,
+                                device=query.device)
+    with hip.device_guard(query.device):
+        st = L.mevi_sq_scan_topk_f32(hip.ptr(query), nq, dim, hip.ptr(codes) if nd else None, hip.ptr(vmin), hip.ptr(vdiff), bits,
+                                     hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids), nd, nlist, max_list_len,
+                                     hip.ptr(probe), None if probe_score is None else hip.ptr(probe_score), nprobe, k,
+                                     hip.ptr(out_s), hip.ptr(out_i), hip.ptr(workspace) if workspace.numel() else None,
+                                     workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_sq_scan_topk_f32")
+    return out_s, out_i
+
+
 GRAPH_MAX_EF = 4096                 # MEVI_GRAPH_MAX_EF: entries of a walk's candidate list
 GRAPH_MAX_BATCH = 2048              # MEVI_GRAPH_MAX_BATCH: width * degree, the ids one step of a walk reads
 GRAPH_LINK_MIN_ROWS = 4096          # MEVI_GRAPH_LINK_MIN_ROWS: destination rows the smallest link workspace holds
@@ -707,8 +793,12 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     reverse links, no pruning; seeds from strided entry rows or, with MEVI_HNSW_ENTRY=levels, from a descent through
     deterministic upper levels; efSearch = MEVI_HNSW_EFSEARCH or 16; recall and steps on stderr;
     MEVI_HNSW=exact answers it with the exact search instead, as do dim % 4 != 0, M outside 2..256, topk > 4096 and corpora
-    of fewer than 64 * 2M rows, where a graph of that degree is close to complete); every other index type (HNSW<M>_PQ*,
-    OPQ*, SQ*, ...) is served by exact search (recall >= the approximate index it names).
+    of fewer than 64 * 2M rows, where a graph of that degree is close to complete);
+    "SQ8" / "SQ4" / "IVF<n>,SQ8" / "IVF<n>,SQ4" -> one byte or one nibble per dimension with a per-dimension min / max range,
+    decoded inside the list scan on the device (mevi_amd/sq.py; same nprobe and recall report; MEVI_SQ=exact answers them with
+    the exact search instead, as do dim % 4 != 0 (8 bits) / dim % 8 != 0 (4 bits), dim > 4096, nlist > rows and topk > 4096);
+    every other index type (HNSW<M>_PQ*, OPQ*, SQ6, SQfp16, ...) is served by exact search (recall >= the approximate index it
+    names).
     Returns numpy (dists f32[nq,topk], indices i64[nq,topk]).
     """
     hip.require_gpu()
@@ -716,15 +806,18 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     print(f"Param {param} trained: {is_trained_before_train(param)}.")  # index.is_trained before index.train
     q = _as_device_f32(np.asarray(query).reshape(-1, dim) if isinstance(query, np.ndarray) else query, device)
     d = _as_device_f32(np.asarray(doc).reshape(-1, dim) if isinstance(doc, np.ndarray) else doc, device)
-    from . import hnsw, ivf, ivfpq
+    from . import hnsw, ivf, ivfpq, sq
 
     nlist = ivf.parse_factory(param)
     pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+    sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
     if nlist is not None and topk <= MAX_K and 0 < nlist <= d.shape[0]:
         s, i = ivf.search(q, d, topk, nlist)
     elif pq is not None:
         s, i = ivfpq.search(q, d, topk, *pq)
+    elif sq_spec is not None:
+        s, i = sq.search(q, d, topk, *sq_spec)
     elif links is not None:
         s, i = hnsw.search(q, d, topk, links)
     elif topk > MAX_K:
@@ -741,7 +834,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
     Every search takes the batch from host memory and returns numpy arrays, like faiss's API.  Returns the `all_time` dict."""
     import time
 
-    from . import hnsw, ivf, ivfpq
+    from . import hnsw, ivf, ivfpq, sq
 
     hip.require_gpu()
     device = torch.device(device if device is not None else "cuda")
@@ -758,17 +851,24 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         upload = time.time() - t
         use_ivf = nlist is not None and 0 < nlist <= d.shape[0] and topk <= MAX_K
         pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+        sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         t = time.time()
         cent = ivf.train_centroids(d, nlist) if use_ivf else None      # index.train(doc)
         if pq is not None:                                             # ... of the coarse and the product quantiser
             cent = ivf.train_centroids(d, pq[0]) if pq[0] is not None else None
             book = ivfpq.train_codebook(d, ivf.assign(d, cent) if cent is not None else None, cent, pq[1], pq[2])
+        if sq_spec is not None:                                        # ... of the coarse quantiser and the range
+            cent = ivf.train_centroids(d, sq_spec[0]) if sq_spec[0] is not None else None
+            sq_range = sq.train_range(d, ivf.assign(d, cent) if cent is not None else None, cent)
         torch.cuda.synchronize()
         all_time["train"] += time.time() - t
         t = time.time()
         links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
         if pq is not None:                                             # index.add(doc): lists and codes
             index = ivfpq.IVFPQIndex(d, pq[0], pq[1], pq[2], centroids=cent, codebook=book)
+            use_ivf = True
+        elif sq_spec is not None:                                      # index.add(doc): lists and codes
+            index = sq.SQIndex(d, sq_spec[0], sq_spec[1], centroids=cent, vmin=sq_range[0], vdiff=sq_range[1])
             use_ivf = True
         elif links is not None and not use_ivf:                        # index.add(doc): kNN lists, links, entry rows
             index = hnsw.HNSWIndex(d, links)

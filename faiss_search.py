@@ -6,7 +6,9 @@ MEVI/faiss_search.py:80-98, served by the MI355X inner-product top-k instead of 
 builds an IVF-Flat index with faiss's structure and defaults (mevi_amd/ivf.py; nprobe from MEVI_IVF_NPROBE, default 1)
 and reports its recall against the exact search on stderr; "IVF<n>,PQ<m>[x<b>]" and "PQ<m>[x<b>]" (b <= 8) build
 product-quantised lists searched by ADC on the device (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact or a
-shape outside the index's envelope gives the exact search instead); "HNSW<M>" builds a neighbour graph walked on the device
+shape outside the index's envelope gives the exact search instead); "IVF<n>,PQ<m>x4fs" and "PQ<m>x4fs" build the same index at
+4 bits with two codes per byte and a scan free of LDS bank conflicts (mevi_amd/pqfs.py; f32 tables and residual codes: the results of
+"PQ<m>x4", not faiss's u8-quantised tables; MEVI_PQFS=exact or a shape outside the envelope gives the exact search); "HNSW<M>" builds a neighbour graph walked on the device
 (mevi_amd/hnsw.py; efSearch from MEVI_HNSW_EFSEARCH, default 16; MEVI_HNSW_ENTRY=levels seeds the walk by descending
 deterministic upper levels instead of scanning strided entry rows; MEVI_HNSW=exact gives the exact search instead); "SQ8", "SQ4",
 "IVF<n>,SQ8" and "IVF<n>,SQ4" build scalar-quantised rows (one byte or one nibble per dimension) decoded inside the list scan on

@@ -176,6 +176,11 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
  * workspace cap, declared and documented in mevi_hip_ivfpq.h. */
 #include "mevi_hip_ivfpq.h"
 
+/* 4-bit fast-scan PQ ("IVF<n>,PQ<m>x4fs", "PQ<m>x4fs"): two codes per byte -- the packer and the ADC scan over packed rows, which
+ * returns the bits of the scan above at K = 16 -- with the sizing functions and the same workspace cap, declared and documented in
+ * mevi_hip_pqfs.h. */
+#include "mevi_hip_pqfs.h"
+
 /* Scalar-quantised rows ("SQ8", "SQ4", "IVF<n>,SQ8", "IVF<n>,SQ4"): the encoder and the list scan that decodes one byte or one
  * nibble per dimension in registers, with the sizing functions and the workspace cap of the scan above, declared and documented in
  * mevi_hip_sq.h. */

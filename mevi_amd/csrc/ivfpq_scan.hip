@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "ivf_select.h"
+#include "ivfpq_tables.h"
 
 namespace mevi {
 namespace {
@@ -88,41 +89,14 @@ const char *ivfpq_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t dim, int64
   return nullptr;
 }
 
-// ---- clean ------------------------------------------------------------------------------------------------------------
-// One thread per (query of the tile, slot): the slot survives when its list exists and no earlier slot of the row names it.
+// ---- clean, lookup tables: ivfpq_tables.h (shared with pqfs_scan.hip) ---------------------------------------------------
 __global__ void ivfpq_clean_kernel(const int32_t *__restrict__ probe, int qn, int nprobe, int nlist, int32_t *__restrict__ clean) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= qn * nprobe) return;
-  const int q = i / nprobe, s = i - q * nprobe;
-  const int32_t *row = probe + (size_t)q * nprobe;
-  const int l = row[s];
-  bool ok = l >= 0 && l < nlist;
-  for (int t = 0; ok && t < s; ++t) ok = row[t] != l;
-  clean[i] = ok ? l : -1;
+  ivfpq_clean_body(probe, qn, nprobe, nlist, clean);
 }
 
-// ---- lookup tables ----------------------------------------------------------------------------------------------------
-// One thread per table entry (query, j, c); consecutive threads take consecutive c, so the store is coalesced and the query
-// slice is one address per wave (K >= 64) or a few.
 __global__ void __launch_bounds__(256) ivfpq_lut_kernel(const float *__restrict__ query, const float *__restrict__ codebook, int qn,
                                                         int dim, int m, int K, int dsub, float *__restrict__ lut) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int per_q = m * K;
-  if (i >= (long long)qn * per_q) return;
-  const int q = (int)(i / per_q), e = (int)(i - (long long)q * per_q);
-  const int j = e / K;
-  const float *qp = query + (size_t)q * dim + (size_t)j * dsub;
-  const float *cp = codebook + (size_t)e * dsub;                // codebook[j][c] = entry j * K + c
-  float acc = 0.f;
-  for (int t = 0; t < dsub; t += 4) {
-    const float4 a = *reinterpret_cast<const float4 *>(qp + t);
-    const float4 b = *reinterpret_cast<const float4 *>(cp + t);
-    acc = fmaf(a.x, b.x, acc);
-    acc = fmaf(a.y, b.y, acc);
-    acc = fmaf(a.z, b.z, acc);
-    acc = fmaf(a.w, b.w, acc);
-  }
-  lut[i] = acc;
+  ivfpq_lut_body(query, codebook, qn, dim, m, K, dsub, lut);
 }
 
 // ---- scan -------------------------------------------------------------------------------------------------------------

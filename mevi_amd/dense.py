@@ -281,6 +281,80 @@ def ivfpq_scan_topk(query, codebook, codes, list_offsets, row_ids, max_list_len,
     return out_s, out_i
 
 
+PQFS_ROW_BLOCK = 2048               # MEVI_PQFS_SCAN_ROW_BLOCK: rows of a list per work item of the packed 4-bit ADC scan
+PQFS_MIN_M, PQFS_MAX_M = 8, 96      # subspaces (nibbles per row) that scan takes; m % 8 == 0
+
+
+def pqfs_scan_workspace_bytes(nq, nprobe, k, dim, m, nlist, max_list_len):
+    """Bytes of workspace `pqfs_scan_topk` needs (host arithmetic; 0 = shape outside the kernel's envelope); never above
+    IVF_WORKSPACE_CAP."""
+    return int(hip.lib().mevi_pqfs_scan_workspace_bytes(nq, nprobe, k, dim, m, nlist, max_list_len))
+
+
+def pqfs_scan_query_tile(nq, nprobe, k, dim, m, nlist, max_list_len):
+    """Queries per tile of `pqfs_scan_topk` (0 = outside the envelope)."""
+    return int(hip.lib().mevi_pqfs_scan_query_tile(nq, nprobe, k, dim, m, nlist, max_list_len))
+
+
+def pq4_pack(codes, out=None):
+    """u8 [n, m / 2]: the 4-bit codes u8 [n, m] two to a byte, code 2t in the low nibble of byte t and code 2t + 1 in the high one;
+    only the low 4 bits of an input byte are kept (mevi_pq4_pack).  One launch, stream-ordered."""
+    hip.require_gpu()
+    assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous()
+    n, m = codes.shape
+    assert m % 2 == 0, m
+    if out is None:
+        out = torch.empty((n, m // 2), dtype=torch.uint8, device=codes.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (n, m // 2)
+    with hip.device_guard(codes.device):
+        st = hip.lib().mevi_pq4_pack(hip.ptr(codes) if n else None, n, m, hip.ptr(out) if n else None, hip.stream_ptr())
+    hip.check(st, "mevi_pq4_pack")
+    return out
+
+
+def pqfs_scan_topk(query, codebook, packed, list_offsets, row_ids, max_list_len, probe, probe_score, k, out=None, workspace=None):
+    """Top-k of every query among the rows of the lists its probe row names, scored by ADC over packed 4-bit codes
+    (mevi_pqfs_scan_topk_f32): the bits of `ivfpq_scan_topk` over the unpacked codes with K = 16.
+
+    query f32 [nq, dim]; codebook f32 [m, 16, dim / m]; packed u8 [nd, m / 2] list-major (`pq4_pack`); list_offsets i64
+    [nlist + 1] on the device; row_ids i64 [nd] or None (id = row); probe i32 [nq, nprobe] (entries outside [0, nlist) are empty,
+    a repeated list counts once, at its first slot); probe_score f32 [nq, nprobe] or None: the bias of every slot (None = +0).
+    Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
+    `out` = (scores, ids) and `workspace` (uint8, pqfs_scan_workspace_bytes) preallocated nothing is allocated either."""
+    hip.require_gpu()
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    assert codebook.is_cuda and codebook.dtype == torch.float32 and codebook.dim() == 3 and codebook.is_contiguous()
+    assert codebook.shape[1] == 16 and codebook.shape[0] * codebook.shape[2] == query.shape[1]
+    assert packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 2 and packed.is_contiguous()
+    assert packed.shape[1] * 2 == codebook.shape[0]
+    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
+    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
+    assert probe_score is None or (probe_score.is_cuda and probe_score.dtype == torch.float32 and probe_score.is_contiguous() and
+                                   probe_score.shape == probe.shape)
+    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == packed.shape[0])
+    nq, dim = query.shape
+    m = codebook.shape[0]
+    nd, nlist, nprobe = packed.shape[0], list_offsets.numel() - 1, probe.shape[1]
+    L = hip.lib()
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
+    out_s, out_i = out
+    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    if nq == 0:
+        return out_s, out_i
+    if workspace is None:
+        workspace = torch.empty(L.mevi_pqfs_scan_workspace_bytes(nq, nprobe, k, dim, m, nlist, max_list_len), dtype=torch.uint8,
+                                device=query.device)
+    with hip.device_guard(query.device):
+        st = L.mevi_pqfs_scan_topk_f32(hip.ptr(query), nq, dim, hip.ptr(codebook), m, hip.ptr(packed) if nd else None,
+                                       hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids), nd, nlist, max_list_len,
+                                       hip.ptr(probe), None if probe_score is None else hip.ptr(probe_score), nprobe, k,
+                                       hip.ptr(out_s), hip.ptr(out_i), hip.ptr(workspace) if workspace.numel() else None,
+                                       workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_pqfs_scan_topk_f32")
+    return out_s, out_i
+
+
 SQ_MAX_DIM = 4096                   # columns a scalar-quantised row may have (include/mevi_hip_sq.h)
 
 
@@ -789,6 +863,10 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     "IVF<n>,PQ<m>[x<b>]" / "PQ<m>[x<b>]" (b <= 8) -> product-quantised lists searched by ADC on the device
     (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact answers them with the exact search instead, as do
     shapes outside the index's envelope: dim % m != 0, m % 4 != 0, fewer rows than 2^b, nlist > rows, topk > 4096);
+    "IVF<n>,PQ<m>x4fs" / "PQ<m>x4fs" -> the same index at 4 bits with two codes per byte and a scan whose table gathers cannot
+    meet an LDS bank conflict (mevi_amd/pqfs.py; f32 tables, residual codes: the results of "PQ<m>x4", not faiss's u8 tables;
+    same nprobe and recall report; MEVI_PQFS=exact answers them with the exact search instead, as do dim % m != 0, m % 8 != 0,
+    m outside 8..96, fewer than 16 rows, nlist > rows and topk > 4096);
     "HNSW<M>" / "HNSW<M>,Flat" -> a neighbour graph of degree 2M walked on the device (mevi_amd/hnsw.py: exact kNN links plus
     reverse links, no pruning; seeds from strided entry rows or, with MEVI_HNSW_ENTRY=levels, from a descent through
     deterministic upper levels; efSearch = MEVI_HNSW_EFSEARCH or 16; recall and steps on stderr;
@@ -806,16 +884,19 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     print(f"Param {param} trained: {is_trained_before_train(param)}.")  # index.is_trained before index.train
     q = _as_device_f32(np.asarray(query).reshape(-1, dim) if isinstance(query, np.ndarray) else query, device)
     d = _as_device_f32(np.asarray(doc).reshape(-1, dim) if isinstance(doc, np.ndarray) else doc, device)
-    from . import hnsw, ivf, ivfpq, sq
+    from . import hnsw, ivf, ivfpq, pqfs, sq
 
     nlist = ivf.parse_factory(param)
     pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+    fs = pqfs.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
     if nlist is not None and topk <= MAX_K and 0 < nlist <= d.shape[0]:
         s, i = ivf.search(q, d, topk, nlist)
     elif pq is not None:
         s, i = ivfpq.search(q, d, topk, *pq)
+    elif fs is not None:
+        s, i = pqfs.search(q, d, topk, *fs)
     elif sq_spec is not None:
         s, i = sq.search(q, d, topk, *sq_spec)
     elif links is not None:
@@ -834,7 +915,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
     Every search takes the batch from host memory and returns numpy arrays, like faiss's API.  Returns the `all_time` dict."""
     import time
 
-    from . import hnsw, ivf, ivfpq, sq
+    from . import hnsw, ivf, ivfpq, pqfs, sq
 
     hip.require_gpu()
     device = torch.device(device if device is not None else "cuda")
@@ -852,11 +933,15 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         use_ivf = nlist is not None and 0 < nlist <= d.shape[0] and topk <= MAX_K
         pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+        fs = pqfs.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         t = time.time()
         cent = ivf.train_centroids(d, nlist) if use_ivf else None      # index.train(doc)
         if pq is not None:                                             # ... of the coarse and the product quantiser
             cent = ivf.train_centroids(d, pq[0]) if pq[0] is not None else None
             book = ivfpq.train_codebook(d, ivf.assign(d, cent) if cent is not None else None, cent, pq[1], pq[2])
+        if fs is not None:                                             # ... of the coarse and the 16-centroid product quantiser
+            cent = ivf.train_centroids(d, fs[0]) if fs[0] is not None else None
+            book = ivfpq.train_codebook(d, ivf.assign(d, cent) if cent is not None else None, cent, fs[1], pqfs.NBITS)
         if sq_spec is not None:                                        # ... of the coarse quantiser and the range
             cent = ivf.train_centroids(d, sq_spec[0]) if sq_spec[0] is not None else None
             sq_range = sq.train_range(d, ivf.assign(d, cent) if cent is not None else None, cent)
@@ -866,6 +951,9 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
         if pq is not None:                                             # index.add(doc): lists and codes
             index = ivfpq.IVFPQIndex(d, pq[0], pq[1], pq[2], centroids=cent, codebook=book)
+            use_ivf = True
+        elif fs is not None:                                           # index.add(doc): lists and packed codes
+            index = pqfs.PQFSIndex(d, fs[0], fs[1], centroids=cent, codebook=book)
             use_ivf = True
         elif sq_spec is not None:                                      # index.add(doc): lists and codes
             index = sq.SQIndex(d, sq_spec[0], sq_spec[1], centroids=cent, vmin=sq_range[0], vdiff=sq_range[1])

@@ -207,6 +207,17 @@ _IVFPQ_SIGNATURES = {
 }
 
 
+# include/mevi_hip_pqfs.h (included by mevi_hip.h): packed 4-bit PQ codes, their packer and their ADC scan
+_PQFS_SIGNATURES = {
+    "mevi_pq4_pack": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "mevi_pqfs_scan_workspace_bytes": (c_size_t, [c_int64] * 7),
+    "mevi_pqfs_scan_query_tile": (c_int64, [c_int64] * 7),
+    "mevi_pqfs_scan_topk_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                        c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_void_p]),
+}
+
+
 # include/mevi_hip_sq.h (included by mevi_hip.h): scalar-quantised rows, their encoder and their list scan
 _SQ_SIGNATURES = {
     "mevi_sq_encode_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
@@ -270,10 +281,10 @@ def attn_route_name(route):
 
 def exported_symbols(header="mevi_hip.h"):
     """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h /
-    mevi_hip_ivfpq.h / mevi_hip_sq.h / mevi_hip_graph.h / mevi_hip_graph_levels.h, which it includes)."""
+    mevi_hip_ivfpq.h / mevi_hip_pqfs.h / mevi_hip_sq.h / mevi_hip_graph.h / mevi_hip_graph_levels.h, which it includes)."""
     return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES,
                    "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES, "mevi_hip_sq.h": _SQ_SIGNATURES,
-                   "mevi_hip_graph.h": _GRAPH_SIGNATURES, "mevi_hip_graph_levels.h": _GRAPH_LEVELS_SIGNATURES}[header])
+                   "mevi_hip_pqfs.h": _PQFS_SIGNATURES, "mevi_hip_graph.h": _GRAPH_SIGNATURES, "mevi_hip_graph_levels.h": _GRAPH_LEVELS_SIGNATURES}[header])
 
 
 def lib():
@@ -285,7 +296,7 @@ def lib():
                 "(or __graft_entry__.build()); mevi_amd has no CPU fallback")
         L = ctypes.CDLL(LIB)
         for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES,
-                                  **_SQ_SIGNATURES, **_GRAPH_SIGNATURES, **_GRAPH_LEVELS_SIGNATURES}.items():
+                                  **_PQFS_SIGNATURES, **_SQ_SIGNATURES, **_GRAPH_SIGNATURES, **_GRAPH_LEVELS_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

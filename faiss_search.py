@@ -8,7 +8,11 @@ and reports its recall against the exact search on stderr; "IVF<n>,PQ<m>[x<b>]" 
 product-quantised lists searched by ADC on the device (mevi_amd/ivfpq.py; same nprobe and recall report; MEVI_IVFPQ=exact or a
 shape outside the index's envelope gives the exact search instead); "IVF<n>,PQ<m>x4fs" and "PQ<m>x4fs" build the same index at
 4 bits with two codes per byte and a scan free of LDS bank conflicts (mevi_amd/pqfs.py; f32 tables and residual codes: the results of
-"PQ<m>x4", not faiss's u8-quantised tables; MEVI_PQFS=exact or a shape outside the envelope gives the exact search); "HNSW<M>" builds a neighbour graph walked on the device
+"PQ<m>x4", not faiss's u8-quantised tables; MEVI_PQFS=exact or a shape outside the envelope gives the exact search); "OPQ<M>," in front of either PQ family
+trains faiss's OPQMatrix rotation (device k-means, host float64 SVD) and codes ROTATED residuals, the coarse quantiser staying in
+the input space (mevi_amd/opq.py; one more GEMM on the queries per search; the report adds the trainer's iterations and errors;
+MEVI_OPQ_NITER, default 50; MEVI_OPQ=exact, "OPQ<M>_<dout>" with dout != dim or a shape outside the envelope gives the exact
+search); "HNSW<M>" builds a neighbour graph walked on the device
 (mevi_amd/hnsw.py; efSearch from MEVI_HNSW_EFSEARCH, default 16; MEVI_HNSW_ENTRY=levels seeds the walk by descending
 deterministic upper levels instead of scanning strided entry rows; MEVI_HNSW=exact gives the exact search instead); "SQ8", "SQ4",
 "IVF<n>,SQ8" and "IVF<n>,SQ4" build scalar-quantised rows (one byte or one nibble per dimension) decoded inside the list scan on

@@ -186,6 +186,11 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
  * mevi_hip_sq.h. */
 #include "mevi_hip_sq.h"
 
+/* A learned rotation in front of a product quantiser ("OPQ<M>,PQ<m>", "OPQ<M>,IVF<n>,PQ<m>" and their x4fs forms): rotating
+ * gathered corpus rows and subtracting the rotated centroid of their list in one launch, declared and documented in
+ * mevi_hip_opq.h.  The search side needs no entry point of its own: one mevi_gemm_nt_f32 on the queries, then the scans above. */
+#include "mevi_hip_opq.h"
+
 /* A neighbour graph over the rows ("HNSW<M>"): linking it from exact kNN lists and the best-first search over it, declared and
  * documented in mevi_hip_graph.h. */
 #include "mevi_hip_graph.h"

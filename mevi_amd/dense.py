@@ -441,6 +441,61 @@ def sq_scan_topk(query, codes, vmin, vdiff, bits, list_offsets, row_ids, max_lis
     return out_s, out_i
 
 
+OPQ_MAX_DIM = 4096                  # columns a rotated row may have (include/mevi_hip_opq.h)
+
+
+def opq_rotate_rows(x, rows, list_of, crot, R, out=None, mode=None):
+    """f32 [n, dim]: out[i] = chain(x[rows[i]], R) - crot[list_of[rows[i]]] (rows None: row i; list_of and crot both None: no
+    subtraction), chain = the sequential fmaf chain of `ops.linear` and the subtraction one f32 operation
+    (mevi_opq_rotate_rows_f32: one launch, stream-ordered, nothing but `out` is written).
+
+    x f32 [n_src, dim]; rows i64 [n] or None; list_of i32 [n_src] + crot f32 [nlist, dim] or both None; R f32 [dim, dim] in the
+    nn.Linear layout.  A row id outside [0, n_src) or a list outside [0, nlist) gives a row of zeros.
+    mode (default: MEVI_OPQ_ROTATE or 'fused') = 'steps' composes existing calls instead -- gather, `ops.linear`, gather of crot,
+    subtract: the same bits through three more passes over the chunk (the A/B partner and the reference of the tests)."""
+    hip.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    assert rows is None or (rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous())
+    assert (list_of is None) == (crot is None)
+    n_src, dim = x.shape
+    if crot is not None:
+        assert list_of.is_cuda and list_of.dtype == torch.int32 and list_of.is_contiguous() and list_of.numel() == n_src
+        assert crot.is_cuda and crot.dtype == torch.float32 and crot.is_contiguous() and crot.dim() == 2 and crot.shape[1] == dim
+    assert R.is_cuda and R.dtype == torch.float32 and R.is_contiguous() and R.shape == (dim, dim)
+    n = n_src if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty((n, dim), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (n, dim)
+    if mode is None:
+        mode = os.environ.get("MEVI_OPQ_ROTATE", "fused")
+    if mode not in ("fused", "steps"):
+        raise ValueError(f"MEVI_OPQ_ROTATE={mode!r} is neither 'fused' nor 'steps'")
+    if mode == "steps":
+        if n == 0:
+            return out
+        from . import ops
+
+        src = torch.arange(n, dtype=torch.int64, device=x.device) if rows is None else rows
+        ok = (src >= 0) & (src < n_src)
+        src = torch.where(ok, src, torch.zeros_like(src))
+        if n_src == 0:
+            return out.zero_()
+        with hip.device_guard(x.device):
+            ops.linear(x[src], R, out=out)
+        if crot is not None:
+            lst = list_of[src].long()
+            ok &= (lst >= 0) & (lst < crot.shape[0])
+            torch.sub(out, crot[torch.where(ok, lst, torch.zeros_like(lst))], out=out)
+        return out.masked_fill_(~ok[:, None], 0.0)
+    with hip.device_guard(x.device):
+        st = hip.lib().mevi_opq_rotate_rows_f32(hip.ptr(x) if n_src else None, n_src, dim, None if rows is None else hip.ptr(rows), n,
+                                                None if list_of is None else hip.ptr(list_of), None if crot is None else hip.ptr(crot),
+                                                0 if crot is None else crot.shape[0], hip.ptr(R), hip.ptr(out) if n else None,
+                                                hip.stream_ptr())
+    hip.check(st, "mevi_opq_rotate_rows_f32")
+    return out
+
+
 GRAPH_MAX_EF = 4096                 # MEVI_GRAPH_MAX_EF: entries of a walk's candidate list
 GRAPH_MAX_BATCH = 2048              # MEVI_GRAPH_MAX_BATCH: width * degree, the ids one step of a walk reads
 GRAPH_LINK_MIN_ROWS = 4096          # MEVI_GRAPH_LINK_MIN_ROWS: destination rows the smallest link workspace holds
@@ -875,7 +930,12 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     "SQ8" / "SQ4" / "IVF<n>,SQ8" / "IVF<n>,SQ4" -> one byte or one nibble per dimension with a per-dimension min / max range,
     decoded inside the list scan on the device (mevi_amd/sq.py; same nprobe and recall report; MEVI_SQ=exact answers them with
     the exact search instead, as do dim % 4 != 0 (8 bits) / dim % 8 != 0 (4 bits), dim > 4096, nlist > rows and topk > 4096);
-    every other index type (HNSW<M>_PQ*, OPQ*, SQ6, SQfp16, ...) is served by exact search (recall >= the approximate index it
+    "OPQ<M>,[IVF<n>,]PQ<m>[x<b>]" / "OPQ<M>,[IVF<n>,]PQ<m>x4fs" -> the two PQ families behind a learned orthonormal rotation
+    (mevi_amd/opq.py: faiss OPQMatrix's training loop with the SVD on the host, the coarse quantiser kept in the input space, the
+    product quantiser on rotated residuals, one more GEMM on the queries per search; the report adds the trainer's iterations
+    and errors; MEVI_OPQ=exact answers them with the exact search instead, as do "OPQ<M>_<dout>" with dout != dim, dim % M != 0,
+    dim / M % 4 != 0, fewer than 256 rows, an inner index outside its own envelope and OPQ in front of anything else);
+    every other index type (HNSW<M>_PQ*, SQ6, SQfp16, PCA*, ...) is served by exact search (recall >= the approximate index it
     names).
     Returns numpy (dists f32[nq,topk], indices i64[nq,topk]).
     """
@@ -884,15 +944,18 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     print(f"Param {param} trained: {is_trained_before_train(param)}.")  # index.is_trained before index.train
     q = _as_device_f32(np.asarray(query).reshape(-1, dim) if isinstance(query, np.ndarray) else query, device)
     d = _as_device_f32(np.asarray(doc).reshape(-1, dim) if isinstance(doc, np.ndarray) else doc, device)
-    from . import hnsw, ivf, ivfpq, pqfs, sq
+    from . import hnsw, ivf, ivfpq, opq, pqfs, sq
 
     nlist = ivf.parse_factory(param)
     pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     fs = pqfs.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
+    rot = opq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     if nlist is not None and topk <= MAX_K and 0 < nlist <= d.shape[0]:
         s, i = ivf.search(q, d, topk, nlist)
+    elif rot is not None:
+        s, i = opq.search(q, d, topk, *rot)
     elif pq is not None:
         s, i = ivfpq.search(q, d, topk, *pq)
     elif fs is not None:
@@ -915,7 +978,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
     Every search takes the batch from host memory and returns numpy arrays, like faiss's API.  Returns the `all_time` dict."""
     import time
 
-    from . import hnsw, ivf, ivfpq, pqfs, sq
+    from . import hnsw, ivf, ivfpq, opq, pqfs, sq
 
     hip.require_gpu()
     device = torch.device(device if device is not None else "cuda")
@@ -934,6 +997,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         fs = pqfs.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+        rot = opq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         t = time.time()
         cent = ivf.train_centroids(d, nlist) if use_ivf else None      # index.train(doc)
         if pq is not None:                                             # ... of the coarse and the product quantiser
@@ -945,6 +1009,11 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         if sq_spec is not None:                                        # ... of the coarse quantiser and the range
             cent = ivf.train_centroids(d, sq_spec[0]) if sq_spec[0] is not None else None
             sq_range = sq.train_range(d, ivf.assign(d, cent) if cent is not None else None, cent)
+        if rot is not None:                                            # ... of the rotation, then both quantisers behind it
+            R = opq.train_rotation(d, rot[0])[0]
+            cent = ivf.train_centroids(d, rot[1]) if rot[1] is not None else None
+            book = ivfpq.train_codebook(d, ivf.assign(d, cent) if cent is not None else None, cent, rot[2], rot[3],
+                                        rotation=ivfpq.rotated_centroids(cent, R))
         torch.cuda.synchronize()
         all_time["train"] += time.time() - t
         t = time.time()
@@ -954,6 +1023,9 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
             use_ivf = True
         elif fs is not None:                                           # index.add(doc): lists and packed codes
             index = pqfs.PQFSIndex(d, fs[0], fs[1], centroids=cent, codebook=book)
+            use_ivf = True
+        elif rot is not None:                                          # index.add(doc): lists and codes of rotated residuals
+            index = opq.OPQIndex(d, *rot, R=R, centroids=cent, codebook=book)
             use_ivf = True
         elif sq_spec is not None:                                      # index.add(doc): lists and codes
             index = sq.SQIndex(d, sq_spec[0], sq_spec[1], centroids=cent, vmin=sq_range[0], vdiff=sq_range[1])

@@ -19,6 +19,9 @@ Without IVF there is no coarse quantiser: the residual is the row itself and the
 list, k = nprobe) and the ADC scan (mevi_ivfpq_scan_topk_f32, csrc/ivfpq_scan.hip) with the coarse scores as the bias of every
 probe slot.  Nothing is copied to the host, so up to GRAPH_MAX_QUERIES queries can be captured and replayed (`search_graph`).
 The result is approximate by construction; `search` also runs the exact search and reports recall on stderr.
+
+With `rotation=R` (mevi_amd/opq.py, 'OPQ<M>,...') the product quantiser works behind an orthonormal rotation: lists and coarse
+search are unchanged, the codes are of chain(x, R) - chain(centroid, R), and the scan reads chain(q, R) -- one more GEMM a search.
 """
 import os
 import re
@@ -64,29 +67,55 @@ def wanted(param, nd, dim, topk):
     return spec
 
 
-def train_codebook(docs, list_of, centroids, m, nbits, seed=1234):
-    """The product quantiser: rq.train_pq_codebook on the residuals of at most 256 * K rows drawn from `seed` -> f32 [m, K, dsub]."""
+def rotated_centroids(centroids, R):
+    """The `rotation` pair (R, crot) of an index behind a learned rotation (mevi_amd/opq.py): crot = chain(centroids, R), one
+    `ops.linear`, None without a coarse quantiser."""
+    from . import ops
+
+    R = R.contiguous()
+    return R, (None if centroids is None else ops.linear(centroids, R))
+
+
+def rotate_queries(query, R, buffers=None):
+    """chain(q, R) of a batch of queries: one GEMM launch, into the seventh of a search graph's `buffers` when there are any."""
+    from . import ops
+
+    return ops.linear(query, R, out=None if buffers is None else buffers[6])
+
+
+def train_codebook(docs, list_of, centroids, m, nbits, seed=1234, rotation=None):
+    """The product quantiser: rq.train_pq_codebook on the residuals of at most 256 * K rows drawn from `seed` -> f32 [m, K, dsub].
+    rotation = (R, crot): on the ROTATED residuals chain(x, R) - crot[list of x] of the same rows (dense.opq_rotate_rows)."""
     n = docs.shape[0]
     K = 1 << nbits
     gen = torch.Generator(device=docs.device).manual_seed(int(seed))
     rows = torch.randperm(n, generator=gen, device=docs.device)[:min(n, MAX_POINTS_PER_CENTROID * K)]
-    xs = docs[rows]
-    if centroids is not None:
-        xs = xs - centroids[list_of[rows].long()]
+    if rotation is not None:
+        xs = dense.opq_rotate_rows(docs, rows, None if centroids is None else list_of, rotation[1], rotation[0])
+    else:
+        xs = docs[rows]
+        if centroids is not None:
+            xs = xs - centroids[list_of[rows].long()]
     return rq.train_pq_codebook(xs.contiguous(), m, K, seed=int(seed), n_init=1, max_iter=PQ_NITER)[0].contiguous()
 
 
-def encode(docs, rows, list_of, centroids, codebook, chunk=ENCODE_CHUNK):
+def encode(docs, rows, list_of, centroids, codebook, chunk=ENCODE_CHUNK, rotation=None):
     """u8 [len(rows), m]: the codes of docs[rows] in that order, residuals and codes produced `chunk` rows at a time (never a
-    second f32 copy of the corpus); more than ENCODE_MAX_M subspaces are encoded in groups on contiguous column slices."""
+    second f32 copy of the corpus); more than ENCODE_MAX_M subspaces are encoded in groups on contiguous column slices.
+    rotation = (R, crot): the codes of the rotated residuals, a chunk of them from one dense.opq_rotate_rows call."""
     m, _, dsub = codebook.shape
     n = docs.shape[0] if rows is None else rows.numel()
     codes = torch.empty((n, m), dtype=torch.uint8, device=docs.device)
     for a in range(0, n, chunk):
-        x = docs[a:a + chunk] if rows is None else docs[rows[a:a + chunk]]
-        if centroids is not None:
-            sel = list_of[a:a + chunk] if rows is None else list_of[rows[a:a + chunk]]
-            x = x - centroids[sel.long()]                       # the f32 residual, one rounding per element
+        if rotation is not None:
+            sel = None if centroids is None else (list_of[a:a + chunk] if rows is None else list_of)
+            x = dense.opq_rotate_rows(docs[a:a + chunk] if rows is None else docs, None if rows is None else rows[a:a + chunk], sel,
+                                      rotation[1], rotation[0])
+        else:
+            x = docs[a:a + chunk] if rows is None else docs[rows[a:a + chunk]]
+            if centroids is not None:
+                sel = list_of[a:a + chunk] if rows is None else list_of[rows[a:a + chunk]]
+                x = x - centroids[sel.long()]                   # the f32 residual, one rounding per element
         for g in range(0, m, ENCODE_MAX_M):
             h = min(m, g + ENCODE_MAX_M)
             part = x if (g == 0 and h == m) else x[:, g * dsub:h * dsub]
@@ -97,7 +126,9 @@ def encode(docs, rows, list_of, centroids, codebook, chunk=ENCODE_CHUNK):
 class IVFPQIndex:
     """`index.train(doc); index.add(doc)` of 'IVF<n>,PQ<m>x<b>' (nlist=None: 'PQ<m>x<b>'): centroids, codebook, codes list by list."""
 
-    def __init__(self, docs, nlist, m, nbits=8, centroids=None, codebook=None, seed=1234):
+    def __init__(self, docs, nlist, m, nbits=8, centroids=None, codebook=None, seed=1234, rotation=None):
+        """rotation: None, or an orthonormal R f32 [dim, dim] (mevi_amd/opq.py) -- lists and coarse search stay those of the
+        unrotated rows, the product quantiser codes chain(x, R) - chain(centroid, R) and the scan reads chain(q, R)."""
         assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2
         nd, dim = docs.shape
         assert 1 <= nbits <= 8 and m >= 1 and dim % m == 0, (dim, m, nbits)
@@ -115,10 +146,12 @@ class IVFPQIndex:
             self.list_of = ivf.assign(docs, self.centroids)
             self.offsets, self.offsets_dev, self.ids, self.max_list_len = ivf.build_lists(self.list_of, nlist)
             self.centroid_offsets = torch.tensor([0, nlist], dtype=torch.int64, device=dev)   # the quantiser's one list
-        self.codebook = (train_codebook(docs, self.list_of, self.centroids, m, nbits, seed) if codebook is None
+        self.rotation = None if rotation is None else rotated_centroids(self.centroids, rotation.to(dev))
+        self.codebook = (train_codebook(docs, self.list_of, self.centroids, m, nbits, seed, self.rotation) if codebook is None
                          else codebook.to(dev).contiguous())
         assert self.codebook.shape == (m, self.K, dim // m), (self.codebook.shape, m, self.K, dim)
-        self.codes = encode(docs, None if nlist is None else self.ids, self.list_of, self.centroids, self.codebook)
+        self.codes = encode(docs, None if nlist is None else self.ids, self.list_of, self.centroids, self.codebook,
+                            rotation=self.rotation)
 
     @property
     def n_lists(self):
@@ -137,22 +170,24 @@ class IVFPQIndex:
         return self.search_scan(query.contiguous(), k, self.clamp_nprobe(nprobe))
 
     def search_scan(self, query, k, nprobe, buffers=None):
-        """The two device calls.  `buffers` (search_graph) = preallocated (zero probe, coarse out, i32 probe, out, two workspaces)."""
+        """The two device calls (behind a rotation: one GEMM on the queries first).  `buffers` (search_graph) = preallocated (zero
+        probe, coarse out, i32 probe, out, two workspaces, rotated queries or None)."""
         nq = query.shape[0]
+        rotated = query if self.rotation is None else rotate_queries(query, self.rotation[0], buffers)   # what the ADC scan reads
         if buffers is None:
             zero = torch.zeros((nq, 1), dtype=torch.int32, device=query.device)
             if self.nlist is None:
-                return dense.ivfpq_scan_topk(query, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k)
+                return dense.ivfpq_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k)
             bias, lists = dense.ivf_scan_topk(query, self.centroids, self.centroid_offsets, None, self.nlist, zero, nprobe)
-            return dense.ivfpq_scan_topk(query, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len,
+            return dense.ivfpq_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len,
                                          lists.to(torch.int32), bias, k)
-        zero, coarse, probe, out, ws_coarse, ws_scan = buffers
+        zero, coarse, probe, out, ws_coarse, ws_scan = buffers[:6]
         if self.nlist is None:
-            return dense.ivfpq_scan_topk(query, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k,
+            return dense.ivfpq_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k,
                                          out=out, workspace=ws_scan)
         dense.ivf_scan_topk(query, self.centroids, self.centroid_offsets, None, self.nlist, zero, nprobe, out=coarse, workspace=ws_coarse)
         probe.copy_(coarse[1])
-        return dense.ivfpq_scan_topk(query, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len, probe, coarse[0],
+        return dense.ivfpq_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len, probe, coarse[0],
                                      k, out=out, workspace=ws_scan)
 
     def search_graph(self, nq, k, nprobe=1):
@@ -180,7 +215,8 @@ class SearchGraph:
         buffers = (torch.zeros((nq, 1), dtype=torch.int32, device=dev), (empty(nprobe, torch.float32), empty(nprobe, torch.int64)),
                    empty(nprobe, torch.int32), (empty(k, torch.float32), empty(k, torch.int64)),
                    None if coarse is None else torch.empty(dense.ivf_scan_workspace_bytes(*coarse), dtype=torch.uint8, device=dev),
-                   torch.empty(dense.ivfpq_scan_workspace_bytes(*scan), dtype=torch.uint8, device=dev))
+                   torch.empty(dense.ivfpq_scan_workspace_bytes(*scan), dtype=torch.uint8, device=dev),
+                   None if index.rotation is None else torch.empty_like(self.query))       # the rotated queries
         index.search_scan(self.query, k, nprobe, buffers)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()

@@ -59,7 +59,8 @@ class PQFSIndex:
     """`index.train(doc); index.add(doc)` of 'IVF<n>,PQ<m>x4fs' (nlist=None: 'PQ<m>x4fs'): centroids, codebook, packed codes list
     by list.  `codes` is u8 [nd, m / 2]."""
 
-    def __init__(self, docs, nlist, m, centroids=None, codebook=None, seed=1234):
+    def __init__(self, docs, nlist, m, centroids=None, codebook=None, seed=1234, rotation=None):
+        """rotation: None, or an orthonormal R f32 [dim, dim] (mevi_amd/opq.py), as for IVFPQIndex."""
         assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2
         nd, dim = docs.shape
         assert m >= 2 and m % 2 == 0 and dim % m == 0, (dim, m)
@@ -77,16 +78,17 @@ class PQFSIndex:
             self.list_of = ivf.assign(docs, self.centroids)
             self.offsets, self.offsets_dev, self.ids, self.max_list_len = ivf.build_lists(self.list_of, nlist)
             self.centroid_offsets = torch.tensor([0, nlist], dtype=torch.int64, device=dev)   # the quantiser's one list
-        self.codebook = (ivfpq.train_codebook(docs, self.list_of, self.centroids, m, NBITS, seed) if codebook is None
+        self.rotation = None if rotation is None else ivfpq.rotated_centroids(self.centroids, rotation.to(dev))
+        self.codebook = (ivfpq.train_codebook(docs, self.list_of, self.centroids, m, NBITS, seed, self.rotation) if codebook is None
                          else codebook.to(dev).contiguous())
         assert self.codebook.shape == (m, K, dim // m), (self.codebook.shape, m, K, dim)
         self.codes = torch.empty((nd, m // 2), dtype=torch.uint8, device=dev)
         for a in range(0, nd, PACK_CHUNK):                      # byte codes of a chunk -> its packed rows; the bytes are dropped
             b = min(nd, a + PACK_CHUNK)
             if nlist is None:
-                part = ivfpq.encode(docs[a:b], None, None, None, self.codebook)
+                part = ivfpq.encode(docs[a:b], None, None, None, self.codebook, rotation=self.rotation)
             else:
-                part = ivfpq.encode(docs, self.ids[a:b], self.list_of, self.centroids, self.codebook)
+                part = ivfpq.encode(docs, self.ids[a:b], self.list_of, self.centroids, self.codebook, rotation=self.rotation)
             dense.pq4_pack(part, out=self.codes[a:b])
 
     @property
@@ -106,22 +108,24 @@ class PQFSIndex:
         return self.search_scan(query.contiguous(), k, self.clamp_nprobe(nprobe))
 
     def search_scan(self, query, k, nprobe, buffers=None):
-        """The two device calls.  `buffers` (search_graph) = preallocated (zero probe, coarse out, i32 probe, out, two workspaces)."""
+        """The two device calls (behind a rotation: one GEMM on the queries first).  `buffers` (search_graph) = preallocated (zero
+        probe, coarse out, i32 probe, out, two workspaces, rotated queries or None)."""
         nq = query.shape[0]
+        rotated = query if self.rotation is None else ivfpq.rotate_queries(query, self.rotation[0], buffers)   # what the ADC scan reads
         if buffers is None:
             zero = torch.zeros((nq, 1), dtype=torch.int32, device=query.device)
             if self.nlist is None:
-                return dense.pqfs_scan_topk(query, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k)
+                return dense.pqfs_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k)
             bias, lists = dense.ivf_scan_topk(query, self.centroids, self.centroid_offsets, None, self.nlist, zero, nprobe)
-            return dense.pqfs_scan_topk(query, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len,
+            return dense.pqfs_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len,
                                         lists.to(torch.int32), bias, k)
-        zero, coarse, probe, out, ws_coarse, ws_scan = buffers
+        zero, coarse, probe, out, ws_coarse, ws_scan = buffers[:6]
         if self.nlist is None:
-            return dense.pqfs_scan_topk(query, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k,
+            return dense.pqfs_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, None, self.max_list_len, zero, None, k,
                                         out=out, workspace=ws_scan)
         dense.ivf_scan_topk(query, self.centroids, self.centroid_offsets, None, self.nlist, zero, nprobe, out=coarse, workspace=ws_coarse)
         probe.copy_(coarse[1])
-        return dense.pqfs_scan_topk(query, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len, probe, coarse[0],
+        return dense.pqfs_scan_topk(rotated, self.codebook, self.codes, self.offsets_dev, self.ids, self.max_list_len, probe, coarse[0],
                                     k, out=out, workspace=ws_scan)
 
     def search_graph(self, nq, k, nprobe=1):
@@ -149,7 +153,8 @@ class SearchGraph:
         buffers = (torch.zeros((nq, 1), dtype=torch.int32, device=dev), (empty(nprobe, torch.float32), empty(nprobe, torch.int64)),
                    empty(nprobe, torch.int32), (empty(k, torch.float32), empty(k, torch.int64)),
                    None if coarse is None else torch.empty(dense.ivf_scan_workspace_bytes(*coarse), dtype=torch.uint8, device=dev),
-                   torch.empty(dense.pqfs_scan_workspace_bytes(*scan), dtype=torch.uint8, device=dev))
+                   torch.empty(dense.pqfs_scan_workspace_bytes(*scan), dtype=torch.uint8, device=dev),
+                   None if index.rotation is None else torch.empty_like(self.query))       # the rotated queries
         index.search_scan(self.query, k, nprobe, buffers)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()

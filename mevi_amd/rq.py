@@ -219,6 +219,50 @@ def train_pq_codebook(x, M, K, seed=0, **kw):
     return torch.stack(book), torch.stack(codes, 1).contiguous()
 
 
+PQ_ENCODE_MAX_M = 32              # subspaces of one mevi_pq_encode_f32 call
+
+
+def pq_encode_groups(x, codebook):
+    """`pq_encode` for any number of subspaces: more than PQ_ENCODE_MAX_M are encoded in groups on contiguous column slices."""
+    M, _, dsub = codebook.shape
+    if M <= PQ_ENCODE_MAX_M:
+        return pq_encode(x, codebook)
+    codes = torch.empty((x.shape[0], M), dtype=torch.int32, device=x.device)
+    for g in range(0, M, PQ_ENCODE_MAX_M):
+        h = min(M, g + PQ_ENCODE_MAX_M)
+        codes[:, g:h] = pq_encode(x[:, g * dsub:h * dsub].contiguous(), codebook[g:h].contiguous())
+    return codes
+
+
+def pq_lloyd(x, codebook, iters):
+    """`iters` Lloyd iterations of every subspace's k-means on x f32[n, M * dsub], started from `codebook` f32[M, K, dsub]: assign
+    (mevi_pq_encode_f32, lowest index on ties), then the means of every subspace's clusters (mevi_cluster_means_f32; an empty
+    cluster keeps its old centre).  The count is fixed and nothing is read back to the host: the inner loop of the OPQ rotation
+    trainer (mevi_amd/opq.py), which hot-starts it from the codebook of the previous rotation.  Returns the new codebook."""
+    hip.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and codebook.dtype == torch.float32
+    M, K, dsub = codebook.shape
+    n = x.shape[0]
+    assert x.shape[1] == M * dsub, (x.shape, codebook.shape)
+    x = x.contiguous()
+    parts = x.view(n, M, dsub).permute(1, 0, 2).contiguous()       # [M, n, dsub]: cluster_means reads contiguous rows
+    L = hip.lib()
+    nbytes = L.mevi_cluster_means_workspace_bytes(n, dsub, K)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device)
+    counts = torch.empty(K, dtype=torch.int32, device=x.device)
+    book = codebook.contiguous()
+    for _ in range(int(iters)):
+        codes = pq_encode_groups(x, book)
+        new = torch.empty_like(book)
+        with hip.device_guard(x.device):
+            for j in range(M):
+                st = L.mevi_cluster_means_f32(hip.ptr(parts[j]), n, dsub, hip.ptr(codes[:, j]), M, K, hip.ptr(book[j]), hip.ptr(new[j]),
+                                              hip.ptr(counts), None, hip.ptr(ws), nbytes, hip.stream_ptr())
+                hip.check(st, "mevi_cluster_means_f32")
+        book = new
+    return book
+
+
 class ClusterIndex:
     """CSR form of the reference's `pq_doc_cluster: dict[tuple -> list[int]]` and
     `pq_mapping: dict[int -> tuple]` (MEVI/main_models.py:3200-3220).

@@ -1,4 +1,4 @@
-// Exact top-k of one workgroup's candidates without sorting them all: shared by ivf_select_kernel (ivf_scan.hip) and
+// Exact top-k of one workgroup's candidates without sorting them all: shared by ivf_select_kernel (list_scan.hip) and
 // fine_select_kernel (fine_topk.hip).  A histogram linear in the score narrows the k-th largest score to one of 2048 bins, a
 // radix select (11 + 11 + 10 bits, LDS histograms) inside the bin finds it; when that score's run of equals is cut, a second
 // radix select over the ids of the run picks the lowest ones; the <= k winners are gathered as (score, ~id) keys, padded

@@ -2,10 +2,11 @@
 // QT_4bit, inner product): the encoder mevi_sq_encode_f32 and the list scan mevi_sq_scan_topk_f32.
 //
 // The scan is mevi_ivf_scan_topk_f32 (ivf_scan.hip) with operand A decoded in registers.  Per tile of queries: the grouping of
-// ivf_group.h ((query, slot) pairs by list: memset, mark, plan, scatter), then
-//   scan        the same persistent kernel over (list, tile of 64 pairs, block of 128 rows) items, contiguous per XCD.  A wave
-//               owns 32 rows x 64 pairs on v_mfma_f32_32x32x2_f32; lane half h feeds k = 2j + h, so a score is the sequential
-//               fmaf chain over d = 0..dim-1 from +0 of q[d] * x^[d]: the bits of the IVF-Flat scan over the decoded rows.
+// list_scan.h ((query, slot) pairs by list: memset, mark, plan, scatter), then
+//   scan        the same persistent kernel (the body of grouped_scan.h, with the SqRows operand) over (list, tile of 64 pairs,
+//               block of 128 rows) items, contiguous per XCD.  A wave owns 32 rows x 64 pairs on v_mfma_f32_32x32x2_f32; lane
+//               half h feeds k = 2j + h, so a score is the sequential fmaf chain over d = 0..dim-1 from +0 of q[d] * x^[d]:
+//               the bits of the IVF-Flat scan over the decoded rows.
 //               A lane reads the codes of its row 32 dimensions at a time -- 16-byte loads where the row's byte count is a
 //               multiple of 16, dwords otherwise (and for the tail dim % 32) -- and takes from every dword the two bytes, or
 //               the two nibbles per half dword, its half owns.  x^ = vmin[d] + vdiff[d] * T[c], never contracted (sq_decode):
@@ -16,29 +17,21 @@
 //                          cache) as float4 and the lane keeps the even or the odd pair, as it does for the queries.
 //               The one barrier follows the table build, before the item loop; inside the loop waves without rows just go on.
 //               The bias of a (query, slot) pair is one accumulator column: it is added (__fadd_rn) when the column is stored.
-//   select      ivf_select.h, unchanged.
+//   select      ivf_select_kernel (list_scan.hip).
 // Workspace and tiles are ivf_plan()'s, so the cap MEVI_IVF_SCAN_WORKSPACE_CAP holds.
 //
 // The encoder is one pass over the gathered rows: a thread makes one dword of codes (4 dimensions at 8 bits, 8 at 4) from one
 // or two float4 of the row, of its centroid and of the range.
 #include <float.h>
 
-#include <type_traits>
-
 #include "common.h"
-#include "mfma_pp.h"
-#include "ivf_group.h"
-#include "ivf_select.h"
+#include "grouped_scan.h"
+#include "list_scan.h"
 
 namespace mevi {
 namespace {
 
-constexpr int SQ_PAIR_TILE = MEVI_IVF_SCAN_PAIR_TILE;
-constexpr int SQ_ROW_BLOCK = MEVI_IVF_SCAN_ROW_BLOCK;
-constexpr int SQ_SCAN_THREADS = 256;
 constexpr int64_t SQ_MAX_DIM = 4096;
-constexpr int SQ_SCAN_GRID = 768;                        // three workgroups per CU: registers, and 3 x 32 KiB of LDS
-static_assert(SQ_PAIR_TILE == 64 && SQ_ROW_BLOCK == 128, "the scan kernel's wave layout is 4 x (32 rows x 64 pairs)");
 
 // The name of the argument that puts (bits, dim) outside the envelope, or NULL.
 const char *sq_outside(int64_t dim, int64_t bits) {
@@ -116,147 +109,71 @@ __device__ __forceinline__ float sq_decode(float lo, float df, float t) {
   return lo + prod;
 }
 
+// The row operand of grouped_scan.h over scalar-quantised rows: a lane reads the codes of its row 32 dimensions at a time (16-byte
+// loads when WIDE, dwords otherwise, and for the tail) and takes from every dword the two bytes, or the two nibbles per half
+// dword, its half owns.  Tl: this lane's copy of the table of quotients (bank lane & 31); vmin / vdiff are read through uniform
+// addresses as float4.
 template <int BITS, bool WIDE>
-__global__ void __launch_bounds__(SQ_SCAN_THREADS, 3) sq_scan_kernel(const float *__restrict__ query, const uint8_t *__restrict__ codes,
-                                                                  const float *__restrict__ vmin, const float *__restrict__ vdiff,
-                                                                  const float *__restrict__ bias, const int64_t *__restrict__ off,
-                                                                  int dim, int nlist, int nprobe,
-                                                                  const int32_t *__restrict__ pair_off,
-                                                                  const int32_t *__restrict__ item_off,
-                                                                  const int32_t *__restrict__ pair_q,
-                                                                  const int32_t *__restrict__ pair_slot, float *__restrict__ cand,
-                                                                  long long ld, int max_len) {
-  constexpr int LEVELS = 1 << BITS;
-  constexpr int KW = 32 / BITS;                        // dimensions per dword of codes: 4 or 8
-  constexpr int NW = 32 / KW;                          // dwords of codes per chunk of 32 dimensions: 8 or 4
-  __shared__ float T[LEVELS * 32];
-  for (int i = threadIdx.x; i < LEVELS * 32; i += SQ_SCAN_THREADS) T[i] = __fdiv_rn((float)(i >> 5) + 0.5f, (float)(LEVELS - 1));
-  __syncthreads();
-  const int total = item_off[nlist];
-  const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int lo = (int)((long long)total * b / gridDim.x), hi = (int)((long long)total * (b + 1) / gridDim.x);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int half = lane >> 5, col = lane & 31;
-  const float *Tl = T + col;                           // this lane's copy of the table: bank lane & 31
-  const size_t stride = (size_t)dim * BITS / 8;        // bytes of a row
-  int l = -1, l_begin = 0, l_end = 0;                  // the list of the current item and its item range
-  for (int w = lo; w < hi; ++w) {
-    if (l < 0 || w >= l_end) {                         // last l with item_off[l] <= w (lists without items share an offset)
-      int a = 0, z = nlist;                            // invariant: item_off[a] <= w < item_off[z]
-      while (z - a > 1) {
-        const int m = (a + z) >> 1;
-        if (item_off[m] <= w) a = m;
-        else z = m;
+struct SqRows {
+  static constexpr int LEVELS = 1 << BITS;
+  static constexpr int KW = 32 / BITS;                 // dimensions per dword of codes: 4 or 8
+  static constexpr int NW = 32 / KW;                   // dwords of codes per chunk of 32 dimensions: 8 or 4
+  static constexpr int TAIL = KW;
+  const uint8_t *codes;
+  const float *vmin, *vdiff, *Tl;
+  size_t stride;                                       // bytes of a row
+  const uint8_t *cp;
+  struct Chunk {
+    uint32_t cw[NW];
+  };
+  using Tail = uint32_t;
+  __device__ __forceinline__ void seek(long long row) { cp = codes + (size_t)row * stride; }
+  __device__ __forceinline__ void fetch(Chunk &c, int k, int i) const {
+    if (i) return;                                     // the codes of a chunk are few loads: all of them ahead of the query rows
+    const uint8_t *cpk = cp + (size_t)k * BITS / 8;
+    if (WIDE) {
+#pragma unroll
+      for (int i = 0; i < NW / 4; ++i) {
+        const uint4 t = *reinterpret_cast<const uint4 *>(cpk + 16 * i);
+        c.cw[4 * i] = t.x, c.cw[4 * i + 1] = t.y, c.cw[4 * i + 2] = t.z, c.cw[4 * i + 3] = t.w;
       }
-      l = a;
-      l_begin = item_off[l];
-      l_end = item_off[l + 1];
+    } else {
+#pragma unroll
+      for (int i = 0; i < NW; ++i) c.cw[i] = *reinterpret_cast<const uint32_t *>(cpk + 4 * i);
     }
-    const long long row0 = off[l];
-    const int len = (int)min((long long)max_len, off[l + 1] - row0);
-    const int p0 = pair_off[l], cnt = pair_off[l + 1] - p0;
-    const int nrb = (len + SQ_ROW_BLOCK - 1) / SQ_ROW_BLOCK;
-    const int idx = w - l_begin;
-    const int pt = idx / nrb, rb = idx - pt * nrb;
-    const int wrow = rb * SQ_ROW_BLOCK + wave * 32;    // first row of this wave
-    if (wrow >= len) continue;                         // wave-uniform: nothing below synchronises the workgroup
-    const int pbase = pt * SQ_PAIR_TILE;
-    const bool two = pbase + 32 < cnt;                 // wave-uniform: the tile's second 32 pairs exist
-    const int r = min(wrow + col, len - 1);
-    const int pa = min(pbase + col, cnt - 1), pb = min(pbase + 32 + col, cnt - 1);
-    const int qa = pair_q[p0 + pa], qb = pair_q[p0 + pb];
-    const uint8_t *cp = codes + (size_t)(row0 + r) * stride;
-    const float *qpa = query + (size_t)qa * dim, *qpb = query + (size_t)qb * dim;
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
-    auto chain = [&](auto two_c) {
-      constexpr bool TWO = decltype(two_c)::value;
-      // Four dimensions k..k+3: their codes are quarter `part` of `word` (8 bits: the whole dword; 4 bits: its low or high half).
-      auto step = [&](uint32_t word, int part, const float4 &a, const float4 &s, const float4 &u, const float4 &v) {
-        const int sh = 4 * BITS * part + BITS * half;
-        const uint32_t c0 = (word >> sh) & (LEVELS - 1), c1 = (word >> (sh + 2 * BITS)) & (LEVELS - 1);
-        const float d0 = sq_decode(half ? a.y : a.x, half ? s.y : s.x, Tl[c0 * 32]);
-        const float d1 = sq_decode(half ? a.w : a.z, half ? s.w : s.z, Tl[c1 * 32]);
-        const float u0 = half ? u.y : u.x, u1 = half ? u.w : u.z;
-        const float v0 = half ? v.y : v.x, v1 = half ? v.w : v.z;
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(d0, u0, acc0, 0, 0, 0);
-        if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(d0, v0, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(d1, u1, acc0, 0, 0, 0);
-        if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(d1, v1, acc1, 0, 0, 0);
-      };
-      int k = 0;
-      // 32 k at a time: the codes and the query rows of the chunk are all requested before the first MFMA waits for them.
-      for (; k + 32 <= dim; k += 32) {
-        uint32_t cw[NW];
-        float4 u[8], v[8];
-        const uint8_t *cpk = cp + (size_t)k * BITS / 8;
-        if (WIDE) {
-#pragma unroll
-          for (int i = 0; i < NW / 4; ++i) {
-            const uint4 t = *reinterpret_cast<const uint4 *>(cpk + 16 * i);
-            cw[4 * i] = t.x, cw[4 * i + 1] = t.y, cw[4 * i + 2] = t.z, cw[4 * i + 3] = t.w;
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < NW; ++i) cw[i] = *reinterpret_cast<const uint32_t *>(cpk + 4 * i);
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          u[i] = *reinterpret_cast<const float4 *>(qpa + k + 4 * i);
-          v[i] = TWO ? *reinterpret_cast<const float4 *>(qpb + k + 4 * i) : u[i];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          step(cw[i * 4 / KW], i % (KW / 4), *reinterpret_cast<const float4 *>(vmin + k + 4 * i),
-               *reinterpret_cast<const float4 *>(vdiff + k + 4 * i), u[i], v[i]);
-      }
-      for (; k < dim; k += KW) {                         // dim % 32: the same chain, one dword of codes at a time
-        const uint32_t word = *reinterpret_cast<const uint32_t *>(cp + (size_t)k * BITS / 8);
-#pragma unroll
-        for (int j = 0; j < KW / 4; ++j) {
-          const float4 u = *reinterpret_cast<const float4 *>(qpa + k + 4 * j);
-          step(word, j, *reinterpret_cast<const float4 *>(vmin + k + 4 * j), *reinterpret_cast<const float4 *>(vdiff + k + 4 * j), u,
-               TWO ? *reinterpret_cast<const float4 *>(qpb + k + 4 * j) : u);
-        }
-      }
-    };
-    if (two) chain(std::true_type{});
-    else chain(std::false_type{});
-    // C/D map: column (pair) = lane & 31, row = (i & 3) + 8 * (i >> 2) + 4 * half: four consecutive rows per register quad.
-    // The pair's bias is added here, once per score.
-    auto store = [&](const f32x16 &acc, int p, int q) {
-      if (p >= cnt) return;
-      const int slot = pair_slot[p0 + p];
-      float *dst = cand + ((size_t)q * nprobe + slot) * (size_t)ld;
-      const bool biased = bias != nullptr;
-      const float bv = biased ? bias[(size_t)q * nprobe + slot] : 0.f;
-      auto out = [&](float s) { return biased ? __fadd_rn(s, bv) : s; };
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int rr = wrow + 8 * g + 4 * half;
-        if (rr + 3 < len) {
-          *reinterpret_cast<float4 *>(dst + rr) = make_float4(out(acc[4 * g]), out(acc[4 * g + 1]), out(acc[4 * g + 2]), out(acc[4 * g + 3]));
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (rr + e < len) dst[rr + e] = out(acc[4 * g + e]);
-        }
-      }
-    };
-    store(acc0, pbase + col, qa);
-    if (two) store(acc1, pbase + 32 + col, qb);
   }
-}
+  // Four dimensions k..k+3: their codes are quarter `part` of `word` (8 bits: the whole dword; 4 bits: its low or high half).
+  __device__ __forceinline__ void decode(uint32_t word, int part, int k, int half, float &d0, float &d1) const {
+    const float4 a = *reinterpret_cast<const float4 *>(vmin + k), s = *reinterpret_cast<const float4 *>(vdiff + k);
+    const int sh = 4 * BITS * part + BITS * half;
+    const uint32_t c0 = (word >> sh) & (LEVELS - 1), c1 = (word >> (sh + 2 * BITS)) & (LEVELS - 1);
+    d0 = sq_decode(half ? a.y : a.x, half ? s.y : s.x, Tl[c0 * 32]);
+    d1 = sq_decode(half ? a.w : a.z, half ? s.w : s.z, Tl[c1 * 32]);
+  }
+  __device__ __forceinline__ void quad(const Chunk &c, int k, int i, int half, float &d0, float &d1) const {
+    decode(c.cw[i * 4 / KW], i % (KW / 4), k + 4 * i, half, d0, d1);
+  }
+  __device__ __forceinline__ void fetch_tail(Tail &c, int k) const { c = *reinterpret_cast<const uint32_t *>(cp + (size_t)k * BITS / 8); }
+  __device__ __forceinline__ void tail_quad(const Tail &c, int k, int j, int half, float &d0, float &d1) const {
+    decode(c, j, k + 4 * j, half, d0, d1);
+  }
+};
 
-// ---- selection --------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(IVF_SEL_THREADS) sq_select_kernel(const float *__restrict__ cand, long long ld,
-                                                                    const int32_t *__restrict__ clean,
-                                                                    const int64_t *__restrict__ off,
-                                                                    const int64_t *__restrict__ row_ids, int nprobe, int k,
-                                                                    int max_len, float *__restrict__ out_s, int64_t *__restrict__ out_i) {
-  ivf_select_body(cand, ld, clean, off, row_ids, nprobe, k, max_len, out_s, out_i);
+template <int BITS, bool WIDE>
+__global__ void __launch_bounds__(GS_THREADS, 3) sq_scan_kernel(const float *__restrict__ query, const uint8_t *__restrict__ codes,
+                                                             const float *__restrict__ vmin, const float *__restrict__ vdiff,
+                                                             const float *__restrict__ bias, const int64_t *__restrict__ off,
+                                                             int dim, int nlist, int nprobe, const int32_t *__restrict__ pair_off,
+                                                             const int32_t *__restrict__ item_off,
+                                                             const int32_t *__restrict__ pair_q,
+                                                             const int32_t *__restrict__ pair_slot, float *__restrict__ cand,
+                                                             long long ld, int max_len) {
+  constexpr int LEVELS = 1 << BITS;
+  __shared__ float T[LEVELS * 32];
+  for (int i = threadIdx.x; i < LEVELS * 32; i += GS_THREADS) T[i] = __fdiv_rn((float)(i >> 5) + 0.5f, (float)(LEVELS - 1));
+  __syncthreads();
+  grouped_scan_body(SqRows<BITS, WIDE>{codes, vmin, vdiff, T + (threadIdx.x & 31), (size_t)dim * BITS / 8, nullptr}, query, bias, off,
+                    dim, nlist, nprobe, pair_off, item_off, pair_q, pair_slot, cand, ld, max_len);
 }
 
 }  // namespace
@@ -310,23 +227,11 @@ extern "C" int mevi_sq_scan_topk_f32(const float *q, int64_t nq, int64_t dim, co
                                      int64_t nd, int64_t nlist, int64_t max_list_len, const int32_t *probe, const float *probe_score,
                                      int64_t nprobe, int64_t k, float *out_score, int64_t *out_id, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-  MEVI_REQUIRE(nq >= 0 && nd >= 0 && nlist >= 1 && max_list_len >= 0 && dim >= 1, MEVI_ERR_INVALID_ARG,
-               "sq_scan: bad shape nq=%lld nd=%lld nlist=%lld max_list_len=%lld dim=%lld", (long long)nq, (long long)nd,
-               (long long)nlist, (long long)max_list_len, (long long)dim);
+  if (const int refused = scan_refuse("sq_scan", nq, nd, nlist, max_list_len, dim, nprobe, k)) return refused;
   MEVI_REQUIRE(bits == 4 || bits == 8, MEVI_ERR_UNSUPPORTED, "sq_scan: bits=%lld is neither 4 nor 8", (long long)bits);
   MEVI_REQUIRE(!sq_outside(dim, bits), MEVI_ERR_UNSUPPORTED,
                "sq_scan: dim=%lld is no multiple of %d (a dword of %lld-bit codes) or outside 4..%lld", (long long)dim,
                bits == 8 ? 4 : 8, (long long)bits, (long long)SQ_MAX_DIM);
-  MEVI_REQUIRE(k >= 1 && k <= IVF_SEL_MAX_K, MEVI_ERR_UNSUPPORTED, "sq_scan: k=%lld outside 1..%d", (long long)k, IVF_SEL_MAX_K);
-  MEVI_REQUIRE(nprobe >= 1 && nprobe <= 256, MEVI_ERR_UNSUPPORTED, "sq_scan: nprobe=%lld outside 1..256", (long long)nprobe);
-  MEVI_REQUIRE(nd <= 0x7fffffffLL, MEVI_ERR_UNSUPPORTED, "sq_scan: nd=%lld rows: ids must fit 32 bits", (long long)nd);
-  MEVI_REQUIRE(nlist <= 262144, MEVI_ERR_UNSUPPORTED, "sq_scan: nlist=%lld above 262144", (long long)nlist);
-  MEVI_REQUIRE(max_list_len <= nd, MEVI_ERR_INVALID_ARG, "sq_scan: max_list_len=%lld above nd=%lld", (long long)max_list_len,
-               (long long)nd);
-  IvfPlan p;
-  MEVI_REQUIRE(nq == 0 || sq_plan(nq, nprobe, k, dim, bits, nlist, max_list_len, p), MEVI_ERR_UNSUPPORTED,
-               "sq_scan: nprobe * max_list_len = %lld * %lld floats: one query's candidates above the cap of 2 GiB",
-               (long long)nprobe, (long long)max_list_len);
   if (nq == 0) return MEVI_OK;
   MEVI_REQUIRE(q && vmin && vdiff && list_offsets && probe && out_score && out_id && (codes || nd == 0), MEVI_ERR_INVALID_ARG,
                "sq_scan: null pointer");
@@ -337,30 +242,24 @@ extern "C" int mevi_sq_scan_topk_f32(const float *q, int64_t nq, int64_t dim, co
                MEVI_ERR_INVALID_ARG,
                "sq_scan: misaligned pointer (q/vmin/vdiff 16 bytes, codes 16 with row bytes %% 16 == 0 else 4, offsets/ids 8, "
                "probe/scores 4)");
-  MEVI_REQUIRE(workspace && (uintptr_t)workspace % 256 == 0, MEVI_ERR_INVALID_ARG, "sq_scan: workspace null or not 256-byte aligned");
-  MEVI_REQUIRE(workspace_bytes >= p.total, MEVI_ERR_WORKSPACE, "sq_scan: workspace of %zu bytes, %zu needed", workspace_bytes,
-               p.total);
+  IvfPlan p;
+  MEVI_REQUIRE(sq_plan(nq, nprobe, k, dim, bits, nlist, max_list_len, p), MEVI_ERR_UNSUPPORTED, "sq_scan: shape outside the envelope");
+  if (const int refused = scan_refuse_workspace("sq_scan", workspace, workspace_bytes, p.total)) return refused;
 
   hipStream_t st = (hipStream_t)stream;
   char *ws = (char *)workspace;
   float *cand = (float *)(ws + p.cand);
-  int32_t *clean = (int32_t *)(ws + p.clean), *pair_q = (int32_t *)(ws + p.pair_q), *pair_slot = (int32_t *)(ws + p.pair_slot);
-  int32_t *pair_off = (int32_t *)(ws + p.pair_off), *item_off = (int32_t *)(ws + p.item_off);
-  const int64_t row_blocks = (max_list_len + SQ_ROW_BLOCK - 1) / SQ_ROW_BLOCK;
+  const int32_t *clean = (int32_t *)(ws + p.clean), *pair_q = (int32_t *)(ws + p.pair_q), *pair_slot = (int32_t *)(ws + p.pair_slot);
+  const int32_t *pair_off = (int32_t *)(ws + p.pair_off), *item_off = (int32_t *)(ws + p.item_off);
   const auto scan = bits == 8 ? (wide ? sq_scan_kernel<8, true> : sq_scan_kernel<8, false>)
                               : (wide ? sq_scan_kernel<4, true> : sq_scan_kernel<4, false>);
-  for (int64_t q0 = 0; q0 < nq; q0 += p.qt) {
-    const int qn = (int)(nq - q0 < p.qt ? nq - q0 : p.qt);
+  return scan_tiles(nq, p.qt, [&](int64_t q0, int qn) {
     MEVI_HIP_CHECK(ivf_group_tile(p, ws, probe + q0 * nprobe, list_offsets, qn, (int)nprobe, (int)nlist, (int)max_list_len, st));
-    // at most one item per (pair, row block); beyond one round of resident workgroups the persistent loop takes the rest
-    int64_t grid = (int64_t)qn * nprobe * (row_blocks > 0 ? row_blocks : 1);
-    if (grid > SQ_SCAN_GRID) grid = SQ_SCAN_GRID;
-    scan<<<(int)grid, SQ_SCAN_THREADS, 0, st>>>(q + q0 * dim, codes, vmin, vdiff, probe_score ? probe_score + q0 * nprobe : nullptr,
-                                                list_offsets, (int)dim, (int)nlist, (int)nprobe, pair_off, item_off, pair_q,
-                                                pair_slot, cand, (long long)p.ld, (int)max_list_len);
-    sq_select_kernel<<<qn, IVF_SEL_THREADS, 0, st>>>(cand, (long long)p.ld, clean, list_offsets, row_ids, (int)nprobe, (int)k,
-                                                     (int)max_list_len, out_score + q0 * k, out_id + q0 * k);
-  }
-  MEVI_HIP_CHECK(hipGetLastError());
-  return MEVI_OK;
+    scan<<<grouped_scan_grid(qn, nprobe, max_list_len), GS_THREADS, 0, st>>>(
+        q + q0 * dim, codes, vmin, vdiff, probe_score ? probe_score + q0 * nprobe : nullptr, list_offsets, (int)dim, (int)nlist,
+        (int)nprobe, pair_off, item_off, pair_q, pair_slot, cand, (long long)p.ld, (int)max_list_len);
+    ivf_select_launch(cand, (long long)p.ld, clean, list_offsets, row_ids, qn, (int)nprobe, (int)k, (int)max_list_len,
+                      out_score + q0 * k, out_id + q0 * k, st);
+    return MEVI_OK;
+  });
 }

@@ -181,6 +181,26 @@ IVF_WORKSPACE_CAP = (2 << 30) + (160 << 20)     # MEVI_IVF_SCAN_WORKSPACE_CAP
 IVF_MAX_NPROBE = 256
 
 
+def _scan_call(query, dim, list_offsets, probe, probe_score, row_ids, nd, max_list_len, k, out, workspace, workspace_bytes, *fmt):
+    """What the four `*_scan_topk` wrappers share: the checks of the arguments every scan takes, `out` (allocated when None) and
+    its shape, and the workspace (when None: `workspace_bytes(nq, nprobe, k, dim, *fmt, nlist, max_list_len)` bytes, the library's
+    own query with the format's arguments in `fmt`; None stays None when there are no queries)."""
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous() and query.shape[1] == dim
+    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
+    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
+    assert probe_score is None or (probe_score.is_cuda and probe_score.dtype == torch.float32 and probe_score.is_contiguous() and
+                                   probe_score.shape == probe.shape)
+    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == nd)
+    nq, nlist, nprobe = query.shape[0], list_offsets.numel() - 1, probe.shape[1]
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
+    out_s, out_i = out
+    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    if nq and workspace is None:
+        workspace = torch.empty(workspace_bytes(nq, nprobe, k, dim, *fmt, nlist, max_list_len), dtype=torch.uint8, device=query.device)
+    return nq, nlist, nprobe, out_s, out_i, workspace
+
+
 def ivf_scan_workspace_bytes(nq, nprobe, k, dim, nlist, max_list_len):
     """Bytes of workspace `ivf_scan_topk` needs (host arithmetic; 0 = shape outside the kernel's envelope)."""
     return int(hip.lib().mevi_ivf_scan_workspace_bytes(nq, nprobe, k, dim, nlist, max_list_len))
@@ -199,22 +219,13 @@ def ivf_scan_topk(query, docs, list_offsets, row_ids, max_list_len, probe, k, ou
     Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
     `out` = (scores, ids) and `workspace` (uint8, ivf_scan_workspace_bytes) preallocated nothing is allocated either."""
     hip.require_gpu()
-    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
-    assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2 and docs.is_contiguous() and docs.shape[1] == query.shape[1]
-    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
-    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
-    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == docs.shape[0])
-    nq, dim = query.shape
-    nd, nlist, nprobe = docs.shape[0], list_offsets.numel() - 1, probe.shape[1]
     L = hip.lib()
-    if out is None:
-        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
-    out_s, out_i = out
-    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2 and docs.is_contiguous()
+    nd, dim = docs.shape
+    nq, nlist, nprobe, out_s, out_i, workspace = _scan_call(query, dim, list_offsets, probe, None, row_ids, nd, max_list_len, k, out,
+                                                            workspace, L.mevi_ivf_scan_workspace_bytes)
     if nq == 0:
         return out_s, out_i
-    if workspace is None:
-        workspace = torch.empty(L.mevi_ivf_scan_workspace_bytes(nq, nprobe, k, dim, nlist, max_list_len), dtype=torch.uint8, device=query.device)
     with hip.device_guard(query.device):
         st = L.mevi_ivf_scan_topk_f32(hip.ptr(query), nq, hip.ptr(docs), hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids),
                                       nd, nlist, max_list_len, dim, hip.ptr(probe), nprobe, k, hip.ptr(out_s), hip.ptr(out_i),
@@ -249,28 +260,15 @@ def ivfpq_scan_topk(query, codebook, codes, list_offsets, row_ids, max_list_len,
     Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
     `out` = (scores, ids) and `workspace` (uint8, ivfpq_scan_workspace_bytes) preallocated nothing is allocated either."""
     hip.require_gpu()
-    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    L = hip.lib()
     assert codebook.is_cuda and codebook.dtype == torch.float32 and codebook.dim() == 3 and codebook.is_contiguous()
     assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous() and codes.shape[1] == codebook.shape[0]
-    assert codebook.shape[0] * codebook.shape[2] == query.shape[1]
-    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
-    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
-    assert probe_score is None or (probe_score.is_cuda and probe_score.dtype == torch.float32 and probe_score.is_contiguous() and
-                                   probe_score.shape == probe.shape)
-    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == codes.shape[0])
-    nq, dim = query.shape
     m, K = codebook.shape[0], codebook.shape[1]
-    nd, nlist, nprobe = codes.shape[0], list_offsets.numel() - 1, probe.shape[1]
-    L = hip.lib()
-    if out is None:
-        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
-    out_s, out_i = out
-    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    nd, dim = codes.shape[0], m * codebook.shape[2]
+    nq, nlist, nprobe, out_s, out_i, workspace = _scan_call(query, dim, list_offsets, probe, probe_score, row_ids, nd, max_list_len, k, out,
+                                                            workspace, L.mevi_ivfpq_scan_workspace_bytes, m, K)
     if nq == 0:
         return out_s, out_i
-    if workspace is None:
-        workspace = torch.empty(L.mevi_ivfpq_scan_workspace_bytes(nq, nprobe, k, dim, m, K, nlist, max_list_len), dtype=torch.uint8,
-                                device=query.device)
     with hip.device_guard(query.device):
         st = L.mevi_ivfpq_scan_topk_f32(hip.ptr(query), nq, dim, hip.ptr(codebook), m, K, hip.ptr(codes) if nd else None,
                                         hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids), nd, nlist, max_list_len,
@@ -322,29 +320,17 @@ def pqfs_scan_topk(query, codebook, packed, list_offsets, row_ids, max_list_len,
     Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
     `out` = (scores, ids) and `workspace` (uint8, pqfs_scan_workspace_bytes) preallocated nothing is allocated either."""
     hip.require_gpu()
-    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    L = hip.lib()
     assert codebook.is_cuda and codebook.dtype == torch.float32 and codebook.dim() == 3 and codebook.is_contiguous()
-    assert codebook.shape[1] == 16 and codebook.shape[0] * codebook.shape[2] == query.shape[1]
+    assert codebook.shape[1] == 16
     assert packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 2 and packed.is_contiguous()
     assert packed.shape[1] * 2 == codebook.shape[0]
-    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
-    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
-    assert probe_score is None or (probe_score.is_cuda and probe_score.dtype == torch.float32 and probe_score.is_contiguous() and
-                                   probe_score.shape == probe.shape)
-    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == packed.shape[0])
-    nq, dim = query.shape
     m = codebook.shape[0]
-    nd, nlist, nprobe = packed.shape[0], list_offsets.numel() - 1, probe.shape[1]
-    L = hip.lib()
-    if out is None:
-        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
-    out_s, out_i = out
-    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    nd, dim = packed.shape[0], m * codebook.shape[2]
+    nq, nlist, nprobe, out_s, out_i, workspace = _scan_call(query, dim, list_offsets, probe, probe_score, row_ids, nd, max_list_len, k, out,
+                                                            workspace, L.mevi_pqfs_scan_workspace_bytes, m)
     if nq == 0:
         return out_s, out_i
-    if workspace is None:
-        workspace = torch.empty(L.mevi_pqfs_scan_workspace_bytes(nq, nprobe, k, dim, m, nlist, max_list_len), dtype=torch.uint8,
-                                device=query.device)
     with hip.device_guard(query.device):
         st = L.mevi_pqfs_scan_topk_f32(hip.ptr(query), nq, dim, hip.ptr(codebook), m, hip.ptr(packed) if nd else None,
                                        hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids), nd, nlist, max_list_len,
@@ -408,29 +394,16 @@ def sq_scan_topk(query, codes, vmin, vdiff, bits, list_offsets, row_ids, max_lis
     Returns (scores f32 [nq, k] desc, ids i64 [nq, k]; ties by ascending id; -FLT_MAX / -1 padding).  Stream-ordered: with
     `out` = (scores, ids) and `workspace` (uint8, sq_scan_workspace_bytes) preallocated nothing is allocated either."""
     hip.require_gpu()
-    assert bits in (4, 8)
-    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
-    assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous()
-    assert codes.shape[1] * 8 == query.shape[1] * bits
-    for v in (vmin, vdiff):
-        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (query.shape[1],)
-    assert list_offsets.is_cuda and list_offsets.dtype == torch.int64 and list_offsets.is_contiguous()
-    assert probe.is_cuda and probe.dtype == torch.int32 and probe.dim() == 2 and probe.is_contiguous() and probe.shape[0] == query.shape[0]
-    assert probe_score is None or (probe_score.is_cuda and probe_score.dtype == torch.float32 and probe_score.is_contiguous() and
-                                   probe_score.shape == probe.shape)
-    assert row_ids is None or (row_ids.is_cuda and row_ids.dtype == torch.int64 and row_ids.is_contiguous() and row_ids.numel() == codes.shape[0])
-    nq, dim = query.shape
-    nd, nlist, nprobe = codes.shape[0], list_offsets.numel() - 1, probe.shape[1]
     L = hip.lib()
-    if out is None:
-        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device))
-    out_s, out_i = out
-    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    assert bits in (4, 8)
+    assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous()
+    nd, dim = codes.shape[0], codes.shape[1] * 8 // bits
+    for v in (vmin, vdiff):
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (dim,)
+    nq, nlist, nprobe, out_s, out_i, workspace = _scan_call(query, dim, list_offsets, probe, probe_score, row_ids, nd, max_list_len, k, out,
+                                                            workspace, L.mevi_sq_scan_workspace_bytes, bits)
     if nq == 0:
         return out_s, out_i
-    if workspace is None:
-        workspace = torch.empty(L.mevi_sq_scan_workspace_bytes(nq, nprobe, k, dim, bits, nlist, max_list_len), dtype=torch.uint8,
-                                device=query.device)
     with hip.device_guard(query.device):
         st = L.mevi_sq_scan_topk_f32(hip.ptr(query), nq, dim, hip.ptr(codes) if nd else None, hip.ptr(vmin), hip.ptr(vdiff), bits,
                                      hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids), nd, nlist, max_list_len,

@@ -47,7 +47,8 @@ def test_workspace_queries_are_pure_host_arithmetic():
 def test_workspace_and_index_sizes_are_those_of_the_recorded_commit():
     """The five `*_bytes` entry points of the dense search over a grid of shapes (zeros for unsupported shapes included)
     against tests/golden/ip_workspace_bytes.json, recorded by tools/capture_workspace_sizes.py from the commit before the
-    host code's layouts were rewritten: the footprint of a search and of an index is behaviour."""
+    host code's layouts were rewritten: the footprint of a search and of an index is behaviour.  The same for the workspace bytes
+    and the query tile of the four list scans (tests/golden/scan_workspace_sizes.json)."""
     import json
 
     from mevi_amd import hip
@@ -72,6 +73,29 @@ def test_workspace_and_index_sizes_are_those_of_the_recorded_commit():
         wrong = [(s, g, w) for s, g, w in zip(shapes, got, want) if g != w]
         assert not wrong, f"{name}: {len(wrong)} of {len(shapes)} differ, first {wrong[:3]} (shape, now, recorded)"
         assert any(w > 0 for w in want), name
+
+    # The list scans: workspace bytes and query tile of the four families (tests/golden/scan_workspace_sizes.json, recorded from
+    # the commit before their host code was shared): per family the grid formats x nq x nprobe x max_list_len, then the edges.
+    with open(os.path.join(ROOT, "tests", "golden", "scan_workspace_sizes.json")) as f:
+        rec = json.load(f)
+    assert "parent commit" in rec["header"]
+    assert rec["nq"] == [0, 1, 33, 4096, 4097, 6980] and rec["nprobe"] == [1, 16, 256, 257]
+    assert rec["max_list_len"] == [-1, 0, 1000, 200000, 2097152, 2097156] and (rec["k"], rec["nlist"]) == (10, 100)
+    assert rec["formats"] == {"ivf": [[768]], "sq": [[768, 8], [64, 4]], "ivfpq": [[16, 4, 16], [768, 64, 256], [768, 96, 256]],
+                              "pqfs": [[32, 8], [768, 96]]}
+    assert {f: len(e) for f, e in rec["edges"].items()} == {"ivf": 10, "sq": 14, "ivfpq": 16, "pqfs": 14}
+    for family, formats in rec["formats"].items():
+        shapes = [(a, b, rec["k"], *fmt, rec["nlist"], c) for fmt in formats for a in rec["nq"] for b in rec["nprobe"]
+                  for c in rec["max_list_len"]] + [tuple(e) for e in rec["edges"][family]]
+        for what in ("workspace_bytes", "query_tile"):
+            name = f"mevi_{family}_scan_{what}"
+            want = rec[name]
+            assert len(want) == len(shapes), name
+            got = [getattr(L, name)(*s) for s in shapes]
+            wrong = [(s, g, w) for s, g, w in zip(shapes, got, want) if g != w]
+            assert not wrong, f"{name}: {len(wrong)} of {len(shapes)} differ, first {wrong[:3]} (shape, now, recorded)"
+            edges = want[-len(rec["edges"][family]):]
+            assert any(w > 0 for w in edges) and any(w == 0 for w in edges) and any(w > 0 for w in want[:-len(edges)]), name
 
 
 def test_product_path_fails_loudly_without_gpu():

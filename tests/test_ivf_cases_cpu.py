@@ -32,8 +32,9 @@ def test_constants_are_the_kernels():
 
     assert (ic.PAIR_TILE, ic.ROW_BLOCK) == (dense.IVF_PAIR_TILE, dense.IVF_ROW_BLOCK)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    shared = open(os.path.join(root, "mevi_amd", "csrc", "list_scan.h")).read()      # the limits and grid rule of every list scan
+    assert "SCAN_MAX_QT = 4096" in shared and "SCAN_CAND_CAP = (size_t)2 << 30" in shared and "if (grid > 768) grid = 768" in shared
     text = open(os.path.join(root, "mevi_amd", "csrc", "ivf_scan.hip")).read()
-    assert "IVF_MAX_QT = 4096" in text and "IVF_CAND_CAP = (size_t)2 << 30" in text and "if (grid > 768) grid = 768" in text
     assert "base += 1024" in text
 
 

@@ -47,6 +47,7 @@ def _check(cuda, args, k, max_list_len=None, **kw):
     (80, 20, 256, 65, 5000, 8, 8, 4096),    # eight draws of eight lists: repeats, some 3300 probed rows a query: padding
     (768, 64, 256, 257, 3000, 10, 1, 10),   # the C2 index shape: 16-byte code loads, a 64 KiB table
     (768, 96, 256, 5, 2000, 10, 3, 100),    # the 96 KiB table (dynamic LDS above 64 KiB)
+    (64, 16, 100, 33, 1500, 6, 2, 50),      # 16-byte code loads with K != 256: codes clamped to K - 1 at run time
 ])
 def test_scan_equals_adc_expected_over_shapes(cuda, dim, m, K, nq, nd, nlist, nprobe, k):
     args = pc.random_index(dim * 3 + m + nq, dim, m, K, nq, nd, nlist, nprobe, repeats=k == 4096)

@@ -1,7 +1,8 @@
 """One IVF-PQ search regime at C2 size, repeated, for a kernel trace: which of the ADC search's kernels the time goes to.
   rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/probe_ivfpq.py [nlist] [nprobe] [nq] [reps] [--docs N]
 (the build's kernels are in the trace too; the search's are ivf_scan_kernel / ivf_select_kernel of the coarse call and
-ivfpq_clean / ivfpq_lut / ivfpq_scan / ivfpq_select)."""
+adc_clean_kernel / adc_lut_kernel / ivfpq_scan_kernel and, again, ivf_select_kernel: select, clean and lut carry one name for every
+family of list scan)."""
 import os
 import sys
 

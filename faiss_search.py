@@ -17,7 +17,12 @@ search); "HNSW<M>" builds a neighbour graph walked on the device
 deterministic upper levels instead of scanning strided entry rows; MEVI_HNSW=exact gives the exact search instead); "SQ8", "SQ4",
 "IVF<n>,SQ8" and "IVF<n>,SQ4" build scalar-quantised rows (one byte or one nibble per dimension) decoded inside the list scan on
 the device (mevi_amd/sq.py; same nprobe and recall report; MEVI_SQ=exact or a shape outside the index's envelope gives the exact
-search instead); any other index type is answered with EXACT search.
+search instead); "<index>,RFlat" and "<index>,Refine(Flat)" behind any of the PQ, x4fs, OPQ and SQ strings above ask that index
+for int(topk * MEVI_REFINE_K_FACTOR) candidates (default factor 1, as faiss) and re-rank them against the original rows on the
+device, so every returned score is the exact search's (mevi_amd/refine.py; the report gives the recall of the refined list and of
+the inner index's own first topk; MEVI_REFINE=exact, more than 4096 candidates, Refine(<anything but Flat>) or a refine behind
+Flat, IVF<n>,Flat or HNSW<M> gives the exact search instead; not sharded under torchrun); any other index type is answered with
+EXACT search.
 With torch.distributed initialised (torchrun) the corpus file is row-sharded across ranks and searched exactly.
 """
 import argparse

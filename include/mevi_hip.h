@@ -291,6 +291,11 @@ int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, in
  * three more entry points under this prefix, with an `_agg` infix, declared and documented in mevi_hip_fine_agg.h. */
 #include "mevi_hip_fine_agg.h"
 
+/* Refine ("...,RFlat" / "...,Refine(Flat)" behind a compressed index): the candidate ids a scan returned, scored against the
+ * original rows with the chain above and cut to the best k in one call, with its two sizing functions, declared and documented
+ * in mevi_hip_refine.h. */
+#include "mevi_hip_refine.h"
+
 /* ------------------------------------------------------------------------
  * Residual-quantisation encode: codes[n, M] (int32, values in [0, K)).
  * Replaces pq.get_rq_document_cluster / the index path of forward_rq with

@@ -469,6 +469,59 @@ def opq_rotate_rows(x, rows, list_of, crot, R, out=None, mode=None):
     return out
 
 
+REFINE_WORKSPACE_CAP = 32 << 20     # MEVI_REFINE_TOPK_WORKSPACE_CAP
+REFINE_MAX_CAND = 16384             # MEVI_REFINE_TOPK_MAX_CAND: candidates of one query (the places of the LDS sort)
+
+
+def refine_topk_workspace_bytes(nq, n_cand, k, dim):
+    """Bytes of workspace `refine_topk` needs (host arithmetic; 0 = shape outside the call's envelope)."""
+    return int(hip.lib().mevi_refine_topk_workspace_bytes(nq, n_cand, k, dim))
+
+
+def refine_topk_query_tile(nq, n_cand, k, dim):
+    """Queries per tile of `refine_topk` (0 = outside the envelope): two launches per tile."""
+    return int(hip.lib().mevi_refine_topk_query_tile(nq, n_cand, k, dim))
+
+
+def refine_topk(query, docs, cand, k, out=None, workspace=None):
+    """The best k of every query's candidate ids by exact score (mevi_refine_topk_f32): faiss IndexRefineFlat's second stage.
+
+    query f32 [nq, dim] and cand i64 [nq, n_cand] may be row-strided views (unit stride inside a row, the query's row stride a
+    multiple of 4); docs f32 [nd, dim] contiguous.  An id outside [0, nd) -- the scans' -1 padding -- is skipped, a repeated id is
+    listed twice.  Returns (scores f32 [nq, k] desc, ids i64 [nq, k], nvalid i32 [nq]): the scores are the bits of the exact search,
+    ties by ascending id, -FLT_MAX / -1 padding.  Stream-ordered: with `out` = (scores, ids, nvalid) and `workspace` (uint8,
+    refine_topk_workspace_bytes) preallocated nothing is allocated either."""
+    hip.require_gpu()
+    L = hip.lib()
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and (query.shape[0] < 2 or query.stride(0) >= query.shape[1])
+    assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2 and docs.is_contiguous() and docs.shape[1] == query.shape[1]
+    assert cand.is_cuda and cand.dtype == torch.int64 and cand.dim() == 2 and cand.shape[0] == query.shape[0]
+    assert (query.shape[1] < 2 or query.stride(1) == 1) and (cand.shape[1] < 2 or cand.stride(1) == 1)
+    nq, dim = query.shape
+    nd, n_cand = docs.shape[0], cand.shape[1]
+    ldq = query.stride(0) if nq > 1 else dim
+    ld_cand = cand.stride(0) if nq > 1 else n_cand
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=query.device), torch.empty((nq, k), dtype=torch.int64, device=query.device),
+               torch.empty((nq,), dtype=torch.int32, device=query.device))
+    out_s, out_i, out_n = out
+    assert out_s.shape == (nq, k) and out_i.shape == (nq, k) and out_s.is_contiguous() and out_i.is_contiguous()
+    assert out_s.dtype == torch.float32 and out_i.dtype == torch.int64
+    assert out_n is None or (out_n.shape == (nq,) and out_n.dtype == torch.int32 and out_n.is_contiguous())
+    if nq and workspace is None:
+        need = L.mevi_refine_topk_workspace_bytes(nq, n_cand, k, dim)
+        if need == 0:
+            raise hip.MeviHipError(f"refine_topk: unsupported shape nq={nq} n_cand={n_cand} k={k} dim={dim}")
+        workspace = torch.empty(need, dtype=torch.uint8, device=query.device)
+    with hip.device_guard(query.device):
+        st = L.mevi_refine_topk_f32(hip.ptr(query) if nq else None, ldq, nq, hip.ptr(docs) if nd else None, nd, dim,
+                                    hip.ptr(cand) if nq else None, ld_cand, n_cand, k, hip.ptr(out_s) if nq else None,
+                                    hip.ptr(out_i) if nq else None, None if out_n is None or not nq else hip.ptr(out_n),
+                                    hip.ptr(workspace) if nq else None, workspace.numel() if nq else 0, hip.stream_ptr())
+    hip.check(st, "mevi_refine_topk_f32")
+    return out_s, out_i, out_n
+
+
 GRAPH_MAX_EF = 4096                 # MEVI_GRAPH_MAX_EF: entries of a walk's candidate list
 GRAPH_MAX_BATCH = 2048              # MEVI_GRAPH_MAX_BATCH: width * degree, the ids one step of a walk reads
 GRAPH_LINK_MIN_ROWS = 4096          # MEVI_GRAPH_LINK_MIN_ROWS: destination rows the smallest link workspace holds
@@ -871,7 +924,8 @@ def sharded_ip_topk(query, local_docs, k, id_offset, group=None, local_search=No
 def is_trained_before_train(param):
     """What `faiss.index_factory(dim, param).is_trained` reports BEFORE `index.train` (the value the reference prints,
     MEVI/faiss_search.py:16): False for every component that learns from data -- IVF coarse quantisers, product /
-    scalar / residual quantisers, OPQ / PCA / ITQ transforms --, True for Flat, HNSW over Flat storage, LSH, IDMap."""
+    scalar / residual quantisers, OPQ / PCA / ITQ transforms --, True for Flat, HNSW over Flat storage, LSH, IDMap.  A refine
+    suffix ('...,RFlat', '...,Refine(Flat)': mevi_amd/refine.py) learns nothing itself: the components before it decide."""
     learns = ("IVF", "IMI", "PQ", "OPQ", "PCA", "ITQ", "SQ", "RQ", "LSQ", "PRQ", "PLSQ")
     for comp in str(param).split(","):
         c = comp.strip()
@@ -908,6 +962,12 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     product quantiser on rotated residuals, one more GEMM on the queries per search; the report adds the trainer's iterations
     and errors; MEVI_OPQ=exact answers them with the exact search instead, as do "OPQ<M>_<dout>" with dout != dim, dim % M != 0,
     dim / M % 4 != 0, fewer than 256 rows, an inner index outside its own envelope and OPQ in front of anything else);
+    "<index>,RFlat" / "<index>,Refine(Flat)" with <index> one of the PQ, x4fs, OPQ and SQ strings above -> that index asked for
+    k_base = int(topk * MEVI_REFINE_K_FACTOR) candidates (default factor 1, as faiss) whose original rows are then scored with the
+    exact search's chain and cut to topk in one device call (mevi_amd/refine.py: every returned score is a bit of the exact
+    search; the report gives the recall of the refined list and of the inner index's own first topk; MEVI_REFINE=exact answers
+    them with the exact search instead, as do k_base > 4096, an inner index outside its own envelope, "Refine(<not Flat>)" and a
+    refine behind Flat, IVF<n>,Flat or HNSW<M>, whose scores are exact already);
     every other index type (HNSW<M>_PQ*, SQ6, SQfp16, PCA*, ...) is served by exact search (recall >= the approximate index it
     names).
     Returns numpy (dists f32[nq,topk], indices i64[nq,topk]).
@@ -917,9 +977,10 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     print(f"Param {param} trained: {is_trained_before_train(param)}.")  # index.is_trained before index.train
     q = _as_device_f32(np.asarray(query).reshape(-1, dim) if isinstance(query, np.ndarray) else query, device)
     d = _as_device_f32(np.asarray(doc).reshape(-1, dim) if isinstance(doc, np.ndarray) else doc, device)
-    from . import hnsw, ivf, ivfpq, opq, pqfs, sq
+    from . import hnsw, ivf, ivfpq, opq, pqfs, refine, sq
 
     nlist = ivf.parse_factory(param)
+    ref = refine.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     fs = pqfs.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
@@ -927,6 +988,8 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     rot = opq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     if nlist is not None and topk <= MAX_K and 0 < nlist <= d.shape[0]:
         s, i = ivf.search(q, d, topk, nlist)
+    elif ref is not None:
+        s, i = refine.search(q, d, topk, *ref)
     elif rot is not None:
         s, i = opq.search(q, d, topk, *rot)
     elif pq is not None:
@@ -951,7 +1014,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
     Every search takes the batch from host memory and returns numpy arrays, like faiss's API.  Returns the `all_time` dict."""
     import time
 
-    from . import hnsw, ivf, ivfpq, opq, pqfs, sq
+    from . import hnsw, ivf, ivfpq, opq, pqfs, refine, sq
 
     hip.require_gpu()
     device = torch.device(device if device is not None else "cuda")
@@ -967,10 +1030,13 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         torch.cuda.synchronize()
         upload = time.time() - t
         use_ivf = nlist is not None and 0 < nlist <= d.shape[0] and topk <= MAX_K
+        ref = refine.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         pq = ivfpq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         fs = pqfs.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         rot = opq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+        if ref is not None:                                            # '<index>,RFlat': train and add are the inner index's
+            pq, fs, rot, sq_spec = (ref[1] if ref[0] == name else None for name in ("ivfpq", "pqfs", "opq", "sq"))
         t = time.time()
         cent = ivf.train_centroids(d, nlist) if use_ivf else None      # index.train(doc)
         if pq is not None:                                             # ... of the coarse and the product quantiser
@@ -1007,6 +1073,8 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
             index = hnsw.HNSWIndex(d, links)
         else:
             index = ivf.IVFFlatIndex(d, nlist, centroids=cent) if use_ivf else (DenseIndex(d) if topk <= MAX_K else None)
+        if ref is not None:                                            # ... the rows are resident already: nothing to add for the refine
+            index = refine.RefineIndex(index, d)
         if isinstance(index, DenseIndex) and any(index.small_image_wanted(b, topk) for b in bs):
             index.prepare_small()                               # the 8-bit image of the small batches is part of index.add
         torch.cuda.synchronize()

@@ -296,6 +296,11 @@ int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, in
  * in mevi_hip_refine.h. */
 #include "mevi_hip_refine.h"
 
+/* Additive (residual) quantiser indexes ("RQ<M>x<b>" / "IVF<n>,RQ<M>x<b>"): full-width lookup tables, the ADC scan over them with
+ * its two sizing functions, and the residual an encoder hands from one group of levels to the next, declared and documented in
+ * mevi_hip_aq.h. */
+#include "mevi_hip_aq.h"
+
 /* ------------------------------------------------------------------------
  * Residual-quantisation encode: codes[n, M] (int32, values in [0, K)).
  * Replaces pq.get_rq_document_cluster / the index path of forward_rq with

@@ -31,17 +31,14 @@
 namespace mevi {
 namespace {
 
-constexpr int IVFPQ_SCAN_THREADS = 512;
-constexpr int64_t IVFPQ_MAX_M = 96;
-constexpr int64_t IVFPQ_MAX_CENTS = 256;
-constexpr size_t IVFPQ_MAX_LUT = (size_t)96 << 10;          // one query's table: what a workgroup keeps in LDS
+constexpr int IVFPQ_SCAN_THREADS = BYTE_SCAN_THREADS;
+constexpr int64_t IVFPQ_MAX_M = BYTE_SCAN_MAX_M;
+constexpr int64_t IVFPQ_MAX_CENTS = BYTE_SCAN_MAX_CENTS;
+constexpr size_t IVFPQ_MAX_LUT = BYTE_SCAN_MAX_LUT;         // one query's table: what a workgroup keeps in LDS
 constexpr size_t IVFPQ_LUT_CAP = (size_t)128 << 20;
 static_assert(MEVI_IVFPQ_SCAN_ROW_BLOCK == 2 * IVFPQ_SCAN_THREADS, "a lane of the scan takes two rows of a block");
 
-struct IvfpqPlan : ScanPlan {
-  size_t lut_bytes;  // one query's table
-  size_t lut, clean; // byte offsets
-};
+using IvfpqPlan = BytePlan;
 
 // Host arithmetic only.  nullptr: inside the envelope; otherwise the name of the first argument outside it.
 const char *ivfpq_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t dim, int64_t m, int64_t K, int64_t nlist,
@@ -49,14 +46,7 @@ const char *ivfpq_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t dim, int64
   if (m < 4 || m > IVFPQ_MAX_M || m % 4 != 0) return "m";
   if (K < 1 || K > IVFPQ_MAX_CENTS || (size_t)m * (size_t)K * sizeof(float) > IVFPQ_MAX_LUT) return "K";
   if (dim < 4 * m || dim % (4 * m) != 0) return "dim";
-  if (const char *outside = scan_plan(nq, nprobe, k, nlist, max_list_len, p)) return outside;
-  p.lut_bytes = (size_t)m * (size_t)K * sizeof(float);
-  const int64_t qlut = (int64_t)(IVFPQ_LUT_CAP / p.lut_bytes);  // queries whose tables fit theirs (>= 1365)
-  if (qlut < p.qt) p.qt = qlut;
-  // a whole cap once tiling by it sets in (not qt * bytes, which would shrink as the bytes grow past a divisor)
-  p.lut = p.take(p.qmax <= qlut ? (size_t)p.qmax * p.lut_bytes : IVFPQ_LUT_CAP);
-  p.clean = p.take((size_t)p.qmax * nprobe * sizeof(int32_t));
-  return nullptr;
+  return byte_scan_plan(nq, nprobe, k, m, K, nlist, max_list_len, p);
 }
 
 // ---- scan -------------------------------------------------------------------------------------------------------------
@@ -97,6 +87,23 @@ __global__ void __launch_bounds__(IVFPQ_SCAN_THREADS) ivfpq_scan_kernel(const fl
 }
 
 }  // namespace
+
+const char *byte_scan_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t m, int64_t K, int64_t nlist, int64_t max_list_len, BytePlan &p) {
+  if (const char *outside = scan_plan(nq, nprobe, k, nlist, max_list_len, p)) return outside;
+  p.lut_bytes = (size_t)m * (size_t)K * sizeof(float);
+  const int64_t qlut = (int64_t)(IVFPQ_LUT_CAP / p.lut_bytes);  // queries whose tables fit theirs (>= 1365)
+  if (qlut < p.qt) p.qt = qlut;
+  // a whole cap once tiling by it sets in (not qt * bytes, which would shrink as the bytes grow past a divisor)
+  p.lut = p.take(p.qmax <= qlut ? (size_t)p.qmax * p.lut_bytes : IVFPQ_LUT_CAP);
+  p.clean = p.take((size_t)p.qmax * nprobe * sizeof(int32_t));
+  return nullptr;
+}
+
+adc_scan_t byte_scan_kernel(bool wide, int64_t K) {
+  return wide ? (K == 256 ? ivfpq_scan_kernel<true, 256> : ivfpq_scan_kernel<true, 0>)
+              : (K == 256 ? ivfpq_scan_kernel<false, 256> : ivfpq_scan_kernel<false, 0>);
+}
+
 }  // namespace mevi
 
 using namespace mevi;
@@ -143,8 +150,7 @@ extern "C" int mevi_ivfpq_scan_topk_f32(const float *q, int64_t nq, int64_t dim,
   MEVI_REQUIRE(!outside, MEVI_ERR_UNSUPPORTED, "ivfpq_scan: %s outside the envelope", outside ? outside : "");
   if (const int refused = scan_refuse_workspace("ivfpq_scan", workspace, workspace_bytes, p.total)) return refused;
 
-  const adc_scan_t scan = wide ? (K == 256 ? ivfpq_scan_kernel<true, 256> : ivfpq_scan_kernel<true, 0>)
-                               : (K == 256 ? ivfpq_scan_kernel<false, 256> : ivfpq_scan_kernel<false, 0>);
+  const adc_scan_t scan = byte_scan_kernel(wide, K);
   const AdcCall call = {q, codebook, probe_score, codes, list_offsets, row_ids, probe, nq, dim, m, K, nd, nlist, max_list_len, nprobe, k,
                         out_score, out_id};
   return adc_scan_tiles(call, p, p.lut, p.clean, (char *)workspace, scan, IVFPQ_SCAN_THREADS, p.lut_bytes, (hipStream_t)stream);

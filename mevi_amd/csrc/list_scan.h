@@ -1,5 +1,6 @@
-// What the four list scans share on the host (ivf_scan.hip, sq_scan.hip: grouped MFMA scans; ivfpq_scan.hip, pqfs_scan.hip: ADC
-// scans): the limits of the envelope, the candidate part of a workspace plan, the refusals every entry point starts with, the
+// What the list scans share on the host (ivf_scan.hip, sq_scan.hip: grouped MFMA scans; ivfpq_scan.hip, pqfs_scan.hip, aq_scan.hip:
+// ADC scans, the last one over the byte-code plan and kernel of the first): the limits of the envelope, the candidate part of a
+// workspace plan, the refusals every entry point starts with, the
 // walk over query tiles, and the launches of the steps that do not depend on the row format -- grouping (ivf_scan.hip), and
 // select, clean and lut (list_scan.hip, one __global__ each: ivf_select_kernel, adc_clean_kernel, adc_lut_kernel).  Every scan
 // hands the same candidate layout cand[query of the tile][slot][row in list] to the selection.
@@ -32,7 +33,7 @@ struct ScanPlan {
 // Host arithmetic only.  nullptr: inside the envelope, p.cand is carved; otherwise the name of the first argument outside it.
 const char *scan_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t nlist, int64_t max_list_len, ScanPlan &p);
 
-// The refusals all four entry points share, in this order: shape (INVALID_ARG), k, nprobe, nd, nlist (UNSUPPORTED),
+// The refusals all entry points share, in this order: shape (INVALID_ARG), k, nprobe, nd, nlist (UNSUPPORTED),
 // max_list_len <= nd (INVALID_ARG), one query's candidates within SCAN_CAND_CAP (UNSUPPORTED).  `name` starts the message.
 int scan_refuse(const char *name, int64_t nq, int64_t nd, int64_t nlist, int64_t max_list_len, int64_t dim, int64_t nprobe, int64_t k);
 int scan_refuse_workspace(const char *name, const void *workspace, size_t workspace_bytes, size_t need);
@@ -83,6 +84,9 @@ void ivf_select_launch(const float *cand, long long ld, const int32_t *clean, co
 // the tile grows, one from 1024 queries on (then a table is loaded once per query).
 using adc_scan_t = void (*)(const float *lut, const uint8_t *codes, const int64_t *off, const int32_t *clean, const float *probe_score,
                             int nprobe, int m, int K, int nrb, float *cand, long long ld, int max_len, long long nd);
+// The table step of a tile: lut[query][j][c] for qn queries.  nullptr: the product quantiser's adc_lut_kernel (codebook
+// [m, K, dim / m]); the additive quantiser hands its full-width tables (aq_scan.hip, codebook [m, K, dim]).
+using adc_lut_t = int (*)(const float *q, const float *codebook, int qn, int dim, int m, int K, float *lut, hipStream_t st);
 struct AdcCall {
   const float *q, *codebook, *probe_score;
   const uint8_t *codes;
@@ -91,8 +95,25 @@ struct AdcCall {
   int64_t nq, dim, m, K, nd, nlist, max_list_len, nprobe, k;
   float *out_score;
   int64_t *out_id;
+  adc_lut_t lut = nullptr;
 };
 int adc_scan_tiles(const AdcCall &c, const ScanPlan &p, size_t lut_off, size_t clean_off, char *ws, adc_scan_t scan, int threads,
                    size_t lds_bytes, hipStream_t st);
+
+// ---- byte codes (ivfpq_scan.hip): what the product and the additive quantiser's scans share ------------------------------------
+constexpr int BYTE_SCAN_THREADS = 512;
+constexpr int64_t BYTE_SCAN_MAX_M = 96;
+constexpr int64_t BYTE_SCAN_MAX_CENTS = 256;
+constexpr size_t BYTE_SCAN_MAX_LUT = (size_t)96 << 10;    // one query's table: what a workgroup keeps in LDS
+
+struct BytePlan : ScanPlan {
+  size_t lut_bytes;  // one query's table
+  size_t lut, clean; // byte offsets
+};
+// Host arithmetic only, for 4 <= m <= 96, m % 4 == 0, K <= 256 and a table within BYTE_SCAN_MAX_LUT (the caller's checks, with
+// its own rule for dim).  nullptr: inside the envelope; otherwise the name of the first argument outside it.
+const char *byte_scan_plan(int64_t nq, int64_t nprobe, int64_t k, int64_t m, int64_t K, int64_t nlist, int64_t max_list_len, BytePlan &p);
+// The scan kernel over rows of m code bytes: wide = m % 16 == 0 (16-byte loads), K = 256 or a run-time K.
+adc_scan_t byte_scan_kernel(bool wide, int64_t K);
 
 }  // namespace mevi

@@ -4,7 +4,8 @@
 //                       cand[query][slot][row in list] of the slots its clean probe row keeps and hands every (score, list-major
 //                       row) to select_topk.h; the <= k winners leave as (score desc, id asc) with -FLT_MAX / -1 padding;
 //   adc_clean_kernel, adc_lut_kernel   the two steps every ADC scan (byte codes, packed 4-bit codes) starts a query tile with;
-//   adc_scan_tiles      the host loop of an ADC call around the family's scan kernel.
+//   adc_scan_tiles      the host loop of an ADC call around the family's scan kernel (and, for the additive quantiser, around its
+//                       own table step: AdcCall::lut).
 // In a trace select, clean and lut carry these names whichever entry point launched them.
 #include <float.h>
 
@@ -162,9 +163,14 @@ int adc_scan_tiles(const AdcCall &c, const ScanPlan &p, size_t lut_off, size_t c
     MEVI_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   return scan_tiles(c.nq, p.qt, [&](int64_t q0, int qn) {
     adc_clean_kernel<<<(qn * nprobe + 255) / 256, 256, 0, st>>>(c.probe + q0 * nprobe, qn, nprobe, (int)c.nlist, clean);
-    const int64_t entries = (int64_t)qn * c.m * c.K;
-    adc_lut_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(c.q + q0 * c.dim, c.codebook, qn, (int)c.dim, (int)c.m, (int)c.K,
-                                                                      (int)(c.dim / c.m), lut);
+    if (c.lut) {                                         // full-width tables: the additive quantiser's own kernels
+      const int status = c.lut(c.q + q0 * c.dim, c.codebook, qn, (int)c.dim, (int)c.m, (int)c.K, lut, st);
+      if (status != MEVI_OK) return status;
+    } else {
+      const int64_t entries = (int64_t)qn * c.m * c.K;
+      adc_lut_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(c.q + q0 * c.dim, c.codebook, qn, (int)c.dim, (int)c.m,
+                                                                        (int)c.K, (int)(c.dim / c.m), lut);
+    }
     int64_t g = (ADC_TARGET_WGS + qn - 1) / qn;
     const int64_t items = nprobe * nrb;
     if (g > items) g = items;

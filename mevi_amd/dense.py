@@ -279,6 +279,86 @@ def ivfpq_scan_topk(query, codebook, codes, list_offsets, row_ids, max_list_len,
     return out_s, out_i
 
 
+AQ_LUT_QUERY_TILE = 256             # MEVI_AQ_LUT_QUERY_TILE: queries of a matrix-core tile of the additive quantiser's tables
+AQ_LUT_FEW_QUERIES = 4              # MEVI_AQ_LUT_FEW_QUERIES: queries of a wave of the few-query table kernel
+
+
+def aq_lut(query, codebook, out=None):
+    """f32 [nq, M, K]: the additive quantiser's lookup tables (mevi_aq_lut_f32), lut[i][j][c] = the sequential fmaf chain
+    <query i, codebook[j][c]> from +0 over all dim columns.  query f32 [nq, dim]; codebook f32 [M, K, dim].  Stream-ordered."""
+    hip.require_gpu()
+    assert query.is_cuda and query.dtype == torch.float32 and query.dim() == 2 and query.is_contiguous()
+    assert codebook.is_cuda and codebook.dtype == torch.float32 and codebook.dim() == 3 and codebook.is_contiguous()
+    M, K, dim = codebook.shape
+    nq = query.shape[0]
+    assert query.shape[1] == dim
+    if out is None:
+        out = torch.empty((nq, M, K), dtype=torch.float32, device=query.device)
+    assert out.shape == (nq, M, K) and out.dtype == torch.float32 and out.is_contiguous()
+    with hip.device_guard(query.device):
+        st = hip.lib().mevi_aq_lut_f32(hip.ptr(query) if nq else None, nq, dim, hip.ptr(codebook), M, K, hip.ptr(out) if nq else None,
+                                       hip.stream_ptr())
+    hip.check(st, "mevi_aq_lut_f32")
+    return out
+
+
+def aq_scan_workspace_bytes(nq, nprobe, k, dim, M, K, nlist, max_list_len):
+    """Bytes of workspace `aq_scan_topk` needs (host arithmetic; 0 = shape outside the kernel's envelope); never above
+    IVF_WORKSPACE_CAP."""
+    return int(hip.lib().mevi_aq_scan_workspace_bytes(nq, nprobe, k, dim, M, K, nlist, max_list_len))
+
+
+def aq_scan_query_tile(nq, nprobe, k, dim, M, K, nlist, max_list_len):
+    """Queries per tile of `aq_scan_topk` (0 = outside the envelope)."""
+    return int(hip.lib().mevi_aq_scan_query_tile(nq, nprobe, k, dim, M, K, nlist, max_list_len))
+
+
+def aq_scan_topk(query, codebook, codes, list_offsets, row_ids, max_list_len, probe, probe_score, k, out=None, workspace=None):
+    """Top-k of every query among the rows of the lists its probe row names, scored by ADC over the byte codes of an additive
+    (residual) quantiser (mevi_aq_scan_topk_f32).  The arguments and the result of `ivfpq_scan_topk` with codebook f32
+    [M, K, dim]: lut[j][c] = the fmaf chain <q, codebook[j][c]> over the whole query, score = ((bias + lut[0][code_0]) +
+    lut[1][code_1]) + ...  Stream-ordered: with `out` and `workspace` (uint8, aq_scan_workspace_bytes) nothing is allocated."""
+    hip.require_gpu()
+    L = hip.lib()
+    assert codebook.is_cuda and codebook.dtype == torch.float32 and codebook.dim() == 3 and codebook.is_contiguous()
+    assert codes.is_cuda and codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous() and codes.shape[1] == codebook.shape[0]
+    M, K, dim = codebook.shape
+    nd = codes.shape[0]
+    nq, nlist, nprobe, out_s, out_i, workspace = _scan_call(query, dim, list_offsets, probe, probe_score, row_ids, nd, max_list_len, k, out,
+                                                            workspace, L.mevi_aq_scan_workspace_bytes, M, K)
+    if nq == 0:
+        return out_s, out_i
+    with hip.device_guard(query.device):
+        st = L.mevi_aq_scan_topk_f32(hip.ptr(query), nq, dim, hip.ptr(codebook), M, K, hip.ptr(codes) if nd else None,
+                                     hip.ptr(list_offsets), None if row_ids is None else hip.ptr(row_ids), nd, nlist, max_list_len,
+                                     hip.ptr(probe), None if probe_score is None else hip.ptr(probe_score), nprobe, k,
+                                     hip.ptr(out_s), hip.ptr(out_i), hip.ptr(workspace) if workspace.numel() else None,
+                                     workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_aq_scan_topk_f32")
+    return out_s, out_i
+
+
+def rq_residual(x, codebook, codes, out=None):
+    """x - codebook[0][codes[:, 0]] - codebook[1][codes[:, 1]] - ... (mevi_rq_residual_f32): one rounded f32 subtraction per
+    level and element, in ascending level.  x f32 [n, dim]; codebook f32 [G, K, dim]; codes i32 [n, >= G] with any row stride
+    (a column slice of a wider code array is fine); out = x works in place.  A code outside [0, K) is clamped to it."""
+    hip.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    assert codebook.is_cuda and codebook.dtype == torch.float32 and codebook.dim() == 3 and codebook.is_contiguous()
+    G, K, dim = codebook.shape
+    n = x.shape[0]
+    assert x.shape[1] == dim and codes.is_cuda and codes.dtype == torch.int32 and codes.dim() == 2 and codes.shape[0] == n
+    assert codes.shape[1] >= G and (n == 0 or codes.stride(1) == 1)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == torch.float32 and out.is_contiguous()
+    with hip.device_guard(x.device):
+        st = hip.lib().mevi_rq_residual_f32(hip.ptr(x) if n else None, n, dim, hip.ptr(codebook), G, K, hip.ptr(codes) if n else None,
+                                            codes.stride(0) if n else G, hip.ptr(out) if n else None, hip.stream_ptr())
+    hip.check(st, "mevi_rq_residual_f32")
+    return out
+
+
 PQFS_ROW_BLOCK = 2048               # MEVI_PQFS_SCAN_ROW_BLOCK: rows of a list per work item of the packed 4-bit ADC scan
 PQFS_MIN_M, PQFS_MAX_M = 8, 96      # subspaces (nibbles per row) that scan takes; m % 8 == 0
 
@@ -962,13 +1042,19 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     product quantiser on rotated residuals, one more GEMM on the queries per search; the report adds the trainer's iterations
     and errors; MEVI_OPQ=exact answers them with the exact search instead, as do "OPQ<M>_<dout>" with dout != dim, dim % M != 0,
     dim / M % 4 != 0, fewer than 256 rows, an inner index outside its own envelope and OPQ in front of anything else);
-    "<index>,RFlat" / "<index>,Refine(Flat)" with <index> one of the PQ, x4fs, OPQ and SQ strings above -> that index asked for
+    "RQ<M>x<b>" / "IVF<n>,RQ<M>x<b>" (b <= 8) -> a residual quantiser: M code bytes a row as "PQ<M>", every code a full-width
+    centroid of what the levels before it leave, searched by ADC with full-width lookup tables (mevi_amd/rqindex.py; greedy
+    encoding and training where faiss keeps a beam of 5; same nprobe and recall report, plus the training error per level;
+    MEVI_RQINDEX=exact answers them with the exact search instead, as do dim % 4 != 0, M % 4 != 0, M outside 4..96, M * 2^b * 4
+    bytes above 96 KiB, fewer rows than 2^b, nlist > rows, topk > 4096, and the strings "RQ<M>" without a width, "RQ..._N<norm>",
+    "RQ1x16-6x8", "LSQ...", "PRQ..." and "OPQ...,RQ...");
+    "<index>,RFlat" / "<index>,Refine(Flat)" with <index> one of the PQ, x4fs, OPQ, SQ and RQ strings above -> that index asked for
     k_base = int(topk * MEVI_REFINE_K_FACTOR) candidates (default factor 1, as faiss) whose original rows are then scored with the
     exact search's chain and cut to topk in one device call (mevi_amd/refine.py: every returned score is a bit of the exact
     search; the report gives the recall of the refined list and of the inner index's own first topk; MEVI_REFINE=exact answers
     them with the exact search instead, as do k_base > 4096, an inner index outside its own envelope, "Refine(<not Flat>)" and a
     refine behind Flat, IVF<n>,Flat or HNSW<M>, whose scores are exact already);
-    every other index type (HNSW<M>_PQ*, SQ6, SQfp16, PCA*, ...) is served by exact search (recall >= the approximate index it
+    every other index type (HNSW<M>_PQ*, SQ6, SQfp16, PCA*, LSQ*, PRQ*, ...) is served by exact search (recall >= the approximate index it
     names).
     Returns numpy (dists f32[nq,topk], indices i64[nq,topk]).
     """
@@ -977,7 +1063,7 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     print(f"Param {param} trained: {is_trained_before_train(param)}.")  # index.is_trained before index.train
     q = _as_device_f32(np.asarray(query).reshape(-1, dim) if isinstance(query, np.ndarray) else query, device)
     d = _as_device_f32(np.asarray(doc).reshape(-1, dim) if isinstance(doc, np.ndarray) else doc, device)
-    from . import hnsw, ivf, ivfpq, opq, pqfs, refine, sq
+    from . import hnsw, ivf, ivfpq, opq, pqfs, refine, rqindex, sq
 
     nlist = ivf.parse_factory(param)
     ref = refine.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
@@ -986,6 +1072,7 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     links = hnsw.wanted(param, d.shape[0], d.shape[1], topk)
     rot = opq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+    rqx = rqindex.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
     if nlist is not None and topk <= MAX_K and 0 < nlist <= d.shape[0]:
         s, i = ivf.search(q, d, topk, nlist)
     elif ref is not None:
@@ -998,6 +1085,8 @@ def search(query, doc, dim, topk, param="Flat", device=None):
         s, i = pqfs.search(q, d, topk, *fs)
     elif sq_spec is not None:
         s, i = sq.search(q, d, topk, *sq_spec)
+    elif rqx is not None:
+        s, i = rqindex.search(q, d, topk, *rqx)
     elif links is not None:
         s, i = hnsw.search(q, d, topk, links)
     elif topk > MAX_K:
@@ -1014,7 +1103,7 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
     Every search takes the batch from host memory and returns numpy arrays, like faiss's API.  Returns the `all_time` dict."""
     import time
 
-    from . import hnsw, ivf, ivfpq, opq, pqfs, refine, sq
+    from . import hnsw, ivf, ivfpq, opq, pqfs, refine, rqindex, sq
 
     hip.require_gpu()
     device = torch.device(device if device is not None else "cuda")
@@ -1035,8 +1124,9 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
         sq_spec = sq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         fs = pqfs.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         rot = opq.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
+        rqx = rqindex.wanted(param, d.shape[0], d.shape[1], topk) if nlist is None else None
         if ref is not None:                                            # '<index>,RFlat': train and add are the inner index's
-            pq, fs, rot, sq_spec = (ref[1] if ref[0] == name else None for name in ("ivfpq", "pqfs", "opq", "sq"))
+            pq, fs, rot, sq_spec, rqx = (ref[1] if ref[0] == name else None for name in ("ivfpq", "pqfs", "opq", "sq", "rqindex"))
         t = time.time()
         cent = ivf.train_centroids(d, nlist) if use_ivf else None      # index.train(doc)
         if pq is not None:                                             # ... of the coarse and the product quantiser
@@ -1053,6 +1143,9 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
             cent = ivf.train_centroids(d, rot[1]) if rot[1] is not None else None
             book = ivfpq.train_codebook(d, ivf.assign(d, cent) if cent is not None else None, cent, rot[2], rot[3],
                                         rotation=ivfpq.rotated_centroids(cent, R))
+        if rqx is not None:                                            # ... of the coarse and the residual quantiser
+            cent = ivf.train_centroids(d, rqx[0]) if rqx[0] is not None else None
+            book = rqindex.train_codebook(d, ivf.assign(d, cent) if cent is not None else None, cent, rqx[1], rqx[2])
         torch.cuda.synchronize()
         all_time["train"] += time.time() - t
         t = time.time()
@@ -1068,6 +1161,9 @@ def profile(query, doc, dim, topk, param, bs=[1, 2, 4, 8], device=None):
             use_ivf = True
         elif sq_spec is not None:                                      # index.add(doc): lists and codes
             index = sq.SQIndex(d, sq_spec[0], sq_spec[1], centroids=cent, vmin=sq_range[0], vdiff=sq_range[1])
+            use_ivf = True
+        elif rqx is not None:                                          # index.add(doc): lists and codes, level group by level group
+            index = rqindex.RQIndex(d, *rqx, centroids=cent, codebook=book)
             use_ivf = True
         elif links is not None and not use_ivf:                        # index.add(doc): kNN lists, links, entry rows
             index = hnsw.HNSWIndex(d, links)

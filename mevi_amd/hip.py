@@ -247,6 +247,16 @@ _REFINE_SIGNATURES = {
 }
 
 
+# include/mevi_hip_aq.h (included by mevi_hip.h): additive (residual) quantiser indexes -- tables, their ADC scan, the encoder's residual
+_AQ_SIGNATURES = {
+    "mevi_aq_lut_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "mevi_aq_scan_workspace_bytes": (c_size_t, [c_int64] * 8),
+    "mevi_aq_scan_query_tile": (c_int64, [c_int64] * 8),
+    "mevi_aq_scan_topk_f32": _IVFPQ_SIGNATURES["mevi_ivfpq_scan_topk_f32"],
+    "mevi_rq_residual_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+}
+
+
 # include/mevi_hip_graph.h (included by mevi_hip.h): the neighbour graph of "HNSW<M>", its linking and its search
 _GRAPH_SIGNATURES = {
     "mevi_graph_link_workspace_bytes": (c_size_t, [c_int64] * 3),
@@ -299,8 +309,9 @@ def attn_route_name(route):
 def exported_symbols(header="mevi_hip.h"):
     """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h /
     mevi_hip_ivfpq.h / mevi_hip_pqfs.h / mevi_hip_sq.h / mevi_hip_opq.h / mevi_hip_graph.h / mevi_hip_graph_levels.h /
-    mevi_hip_refine.h, which it includes)."""
+    mevi_hip_refine.h / mevi_hip_aq.h, which it includes)."""
     return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES, "mevi_hip_refine.h": _REFINE_SIGNATURES,
+                   "mevi_hip_aq.h": _AQ_SIGNATURES,
                    "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES, "mevi_hip_sq.h": _SQ_SIGNATURES,
                    "mevi_hip_pqfs.h": _PQFS_SIGNATURES, "mevi_hip_opq.h": _OPQ_SIGNATURES, "mevi_hip_graph.h": _GRAPH_SIGNATURES, "mevi_hip_graph_levels.h": _GRAPH_LEVELS_SIGNATURES}[header])
 
@@ -315,7 +326,7 @@ def lib():
         L = ctypes.CDLL(LIB)
         for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES,
                                   **_PQFS_SIGNATURES, **_SQ_SIGNATURES, **_OPQ_SIGNATURES, **_GRAPH_SIGNATURES, **_GRAPH_LEVELS_SIGNATURES,
-                                  **_REFINE_SIGNATURES}.items():
+                                  **_REFINE_SIGNATURES, **_AQ_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -8,7 +8,7 @@ the exact search's pinned fmaf chain and an LDS sort.  Every returned score is a
 is which rows were among the candidates.
 
 <index> is one of the compressed families: 'PQ<m>[x<b>]' / 'IVF<n>,PQ<m>[x<b>]' (mevi_amd/ivfpq.py), '...PQ<m>x4fs'
-(mevi_amd/pqfs.py), 'OPQ<M>,...' (mevi_amd/opq.py), 'SQ8' / 'SQ4' / 'IVF<n>,SQ8' / 'IVF<n>,SQ4' (mevi_amd/sq.py).
+(mevi_amd/pqfs.py), 'OPQ<M>,...' (mevi_amd/opq.py), 'SQ8' / 'SQ4' / 'IVF<n>,SQ8' / 'IVF<n>,SQ4' (mevi_amd/sq.py), 'RQ<M>x<b>' / 'IVF<n>,RQ<M>x<b>' (mevi_amd/rqindex.py).
 k_factor = MEVI_REFINE_K_FACTOR (a float, faiss's default 1, below 1 taken as 1), k_base = int(k * k_factor) as in faiss; the
 scans return at most 4096 candidates, so a k_base above that keeps the exact search, as does MEVI_REFINE=exact.
 
@@ -22,9 +22,9 @@ import sys
 
 import torch
 
-from . import dense, hip, ivf, ivfpq, opq, pqfs, sq
+from . import dense, hip, ivf, ivfpq, opq, pqfs, rqindex, sq
 
-FAMILIES = {"opq": opq, "ivfpq": ivfpq, "pqfs": pqfs, "sq": sq}     # in the order their parsers are asked
+FAMILIES = {"opq": opq, "ivfpq": ivfpq, "pqfs": pqfs, "sq": sq, "rqindex": rqindex}     # in the order their parsers are asked
 MAX_K_BASE = 4096                                                    # the list length of the scans
 
 
@@ -35,7 +35,7 @@ def split_factory(param):
 
 
 def parse_factory(param):
-    """(family, inner_spec) of '<index>,RFlat' and '<index>,Refine(Flat)': family in 'opq' / 'ivfpq' / 'pqfs' / 'sq' and inner_spec
+    """(family, inner_spec) of '<index>,RFlat' and '<index>,Refine(Flat)': family in 'opq' / 'ivfpq' / 'pqfs' / 'sq' / 'rqindex' and inner_spec
     what that module's `parse_factory` returns for <index>; else None ('Refine(SQ8)', a refine behind 'Flat' / 'IVF<n>,Flat' /
     'HNSW<M>', two refine suffixes, no suffix)."""
     inner, found = split_factory(param)
@@ -75,8 +75,8 @@ def wanted(param, nd, dim, topk):
 
 
 def build_inner(docs, family, spec, **given):
-    """The inner index of a family: OPQIndex / IVFPQIndex / PQFSIndex / SQIndex(docs, *spec, **given)."""
-    cls = {"opq": opq.OPQIndex, "ivfpq": ivfpq.IVFPQIndex, "pqfs": pqfs.PQFSIndex, "sq": sq.SQIndex}[family]
+    """The inner index of a family: OPQIndex / IVFPQIndex / PQFSIndex / SQIndex / RQIndex(docs, *spec, **given)."""
+    cls = {"opq": opq.OPQIndex, "ivfpq": ivfpq.IVFPQIndex, "pqfs": pqfs.PQFSIndex, "sq": sq.SQIndex, "rqindex": rqindex.RQIndex}[family]
     return cls(docs, *spec, **given)
 
 

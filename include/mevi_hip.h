@@ -191,6 +191,9 @@ int mevi_ivf_scan_topk_f32(const float *q, int64_t nq, const float *docs, const 
  * mevi_hip_opq.h.  The search side needs no entry point of its own: one mevi_gemm_nt_f32 on the queries, then the scans above. */
 #include "mevi_hip_opq.h"
 
+/* ... and the fused form of rotate + encode for the cluster codes of `--pq_type opq` (mevi_opq_encode_f32): mevi_hip_opq_encode.h. */
+#include "mevi_hip_opq_encode.h"
+
 /* A neighbour graph over the rows ("HNSW<M>"): linking it from exact kNN lists and the best-first search over it, declared and
  * documented in mevi_hip_graph.h. */
 #include "mevi_hip_graph.h"

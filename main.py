@@ -2,7 +2,7 @@
 """`python main.py --mode eval ...` -- the argv surface of the reference's MEVI/main.py for the eval
 path that marco_eval_nci_rq.sh drives (MEVI/main.py:356-794, 267-337).  Every flag of that script is
 accepted; the ones that configure training are parsed and ignored.  Only --mode eval with
---codebook 1 --pq_type rq|pq --document_encoder ance|cocondenser|ar2 --query_encoder twin|nci --recall_level both|coarse|fine is built
+--codebook 1 --pq_type rq|pq|opq (opq: with --pq_init_method faiss) --document_encoder ance|cocondenser|ar2 --query_encoder twin|nci --recall_level both|coarse|fine is built
 (+ the brute-force ablation --eval_all_documents 1 --recall_level fine --knn_topk_by_step 1, and --codebook 0 --label_length_cutoff L
 --mapping_path ... --kary K: semantic ids of different lengths over the tower path; and, without --document_encoder, the pure
 NCI baseline over those ids: the beams themselves are ranked, 100 of them by default)
@@ -101,6 +101,11 @@ def parsers_parser(argv=None):
     args.query_embed_accum = given.get("--query_embed_accum", "maxpool")
     if args.query_encoder == "nci":
         ignored = [f for f in ignored if f[0] not in ("--qtower", "--query_embed_accum")]
+    # --pq_init_method (MEVI/main.py:667) is read under --pq_type opq only: 'faiss' is the one value with which the reference's
+    # opq trains at all (pq.py:450-458; its k-means path asserts pq_type != 'opq', pq.py:553)
+    args.pq_init_method = given.get("--pq_init_method", "kmeans")
+    if args.pq_type == "opq":
+        ignored = [f for f in ignored if f[0] != "--pq_init_method"]
     # --codebook 0 (semantic ids): the flags that define the ids, their tree and the clusters (MEVI/main.py:420,559-566,780-787)
     args.label_length_cutoff = int(given.get("--label_length_cutoff", 0))
     args.mapping_path = given.get("--mapping_path")
@@ -182,13 +187,41 @@ EVAL_AFFECTING = {
 }
 
 
-PQ_TYPES = ("rq", "pq")     # cluster codings built: residual and product quantisation (l2)
+PQ_TYPES = ("rq", "pq", "opq")     # cluster codings built: residual, product and rotated product quantisation (l2)
+
+
+def check_opq(a, what):
+    """--pq_type opq: a learned rotation in front of the product quantiser (MEVI/pq.py:67-71, 259-279).  Built for the one
+    configuration in which the reference's opq works, --pq_init_method faiss (what faiss trains for 'OPQ{M},PQ{M}x{bits}' is
+    trained on the device here); the ablations that reach gen_all_reconstruct are refused as the reference refuses them."""
+    if a.pq_type != "opq":
+        return
+    if getattr(a, "pq_init_method", "kmeans") != "faiss":
+        raise SystemExit(f"{what}: --pq_type 'opq' is not built with --pq_init_method {getattr(a, 'pq_init_method', 'kmeans')!r} "
+                         "(rq | pq, or opq together with --pq_init_method faiss: the reference's k-means path asserts "
+                         "pq_type != 'opq', MEVI/pq.py:553)")
+    if getattr(a, "use_topic_model", 0):
+        raise SystemExit(f"{what}: --use_topic_model 1 is not built with --pq_type opq (gen_doc2index_mapping reaches "
+                         "gen_all_reconstruct, which asserts 'Not support OPQ.', MEVI/main_models.py:3303)")
+    if getattr(a, "eval_all_documents", 0):
+        raise SystemExit(f"{what}: --eval_all_documents 1 is not built with --pq_type opq (an ablation of the rq | pq "
+                         "codings; its --use_topic_model form ends in 'Not support OPQ.', MEVI/main_models.py:3303)")
+    if a.subvector_num < 1 or a.subvector_num > 32:
+        raise SystemExit(f"{what}: --pq_type opq takes 1 <= --subvector_num <= 32")
+    width = OPQ_TOWER_WIDTH.get(a.document_encoder)
+    if width is not None and (width % a.subvector_num != 0 or (width // a.subvector_num) % 4 != 0):
+        raise SystemExit(f"{what}: --pq_type opq needs --subvector_num to divide the tower width {width} into slices of a "
+                         f"multiple of 4 columns (got --subvector_num {a.subvector_num})")
+
+
+OPQ_TOWER_WIDTH = {"ance": 768, "cocondenser": 768, "ar2": 768}     # t5-ance (base) and the bert-base towers
 
 
 def check_supported(a):
     if a.mode == "train" and a.only_gen_rq:   # marco_generate_embedding_n_rq.sh: embeddings + RQ codebook + clusters, then exit
         if a.document_encoder not in ("ance", "cocondenser", "ar2") or a.pq_type not in PQ_TYPES or not a.codebook:
-            raise SystemExit("main.py --only_gen_rq 1: needs --codebook 1 --pq_type rq|pq --document_encoder ance|cocondenser|ar2")
+            raise SystemExit("main.py --only_gen_rq 1: needs --codebook 1 --pq_type rq|pq|opq --document_encoder ance|cocondenser|ar2")
+        check_opq(a, "main.py --only_gen_rq 1")
         for k in ("pq_path", "pq_cluster_path", "embedding_path", "document_path", "ckpt_dir"):
             if getattr(a, k) is None:
                 raise SystemExit(f"main.py --only_gen_rq 1: --{k} is required")
@@ -204,8 +237,9 @@ def check_supported(a):
         raise SystemExit(f"main.py --mode eval: --test_set {a.test_set!r} is not built (only 'dev')")
     if a.dataset not in ("marco", "nq_dpr"):
         raise SystemExit(f"main.py --mode eval: --dataset {a.dataset!r} is not built (marco, nq_dpr)")
-    if a.pq_type not in PQ_TYPES:   # opq: its rotation only comes from a faiss index file (MEVI/pq.py:145-151)
-        raise SystemExit(f"main.py --mode eval: --pq_type {a.pq_type!r} is not built (rq | pq)")
+    if a.pq_type not in PQ_TYPES:
+        raise SystemExit(f"main.py --mode eval: --pq_type {a.pq_type!r} is not built (rq | pq | opq with --pq_init_method faiss)")
+    check_opq(a, "main.py --mode eval")
     need = dict(codebook=1)
     if not a.codebook:
         return check_semantic_ids(a)

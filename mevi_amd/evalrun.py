@@ -78,6 +78,13 @@ def split_whole_checkpoint(sd, not_load_document_encoder=False):
     return nci_w, tower, sd.get("pq.codebook")
 
 
+def checkpoint_rotation(sd):
+    """The `pq.rotate` parameter of a whole-model checkpoint (--pq_type opq, MEVI/pq.py:67-71): f32 [dim, dim], or None when the
+    checkpoint carries none.  Beside `split_whole_checkpoint`, whose triple stays as it is."""
+    v = sd.get("pq.rotate")
+    return v if torch.is_tensor(v) else None
+
+
 def attenpool_from_checkpoint(sd):
     """--query_encoder nci --query_embed_accum attenpool: the Linear(d_model, 1) `attenpool_weight` of a whole-model
     checkpoint (T5FineTuner.__init__, MEVI/main_models.py:1314-1315) -> (w f32 [d], b float)."""
@@ -301,6 +308,7 @@ class EvalRun:
         self.pure = bool(getattr(a, "pure_nci", False))
         assert not self.pure or self.semantic
         tower_override, ckpt_codebook = {}, None
+        self._ckpt_rotate = None
         # --query_encoder nci: the fine stage pools the NCI model's own states per (query, beam) (T5FineTuner.clus_repr);
         # the query tower is neither loaded nor run
         self.nci_query = getattr(a, "query_encoder", "twin") == "nci" and not self.pure
@@ -314,6 +322,7 @@ class EvalRun:
         if getattr(a, "infer_ckpt", None):        # whole-model checkpoint (MEVI/main.py:203-230) takes precedence
             sd = _state_dict(a.infer_ckpt)
             nci_w, tower_override, ckpt_codebook = split_whole_checkpoint(sd, bool(getattr(a, "not_load_document_encoder", 0)))
+            self._ckpt_rotate = checkpoint_rotation(sd)
             if self.nci_query and self.qpool_mode & ops.QPOOL_ACCUM["attenpool"]:
                 self.atten = attenpool_from_checkpoint(sd)
             del sd
@@ -439,8 +448,13 @@ class EvalRun:
         self.pq = ProductQuantization(getattr(a, "pq_type", "rq"), self.M, a.subvector_bits, "l2", d_model, device=self.dev)
         if ckpt_codebook is not None:             # --infer_ckpt carries pq.codebook: pq.initialize is skipped (main_models.py:4252)
             self.pq.load_codebook(ckpt_codebook)
+            if self.pq.pq_type == "opq":          # ... and pq.rotate beside it
+                if self._ckpt_rotate is None:
+                    raise SystemExit("--pq_type opq: --infer_ckpt carries pq.codebook but no pq.rotate (the rotation the "
+                                     "codebook was trained behind)")
+                self.pq.load_rotation(self._ckpt_rotate)
         else:
-            self.pq.initialize(a.pq_path, rank=0)
+            self.pq.initialize(a.pq_path, rank=0)           # opq: the {"codebook", "rotate"} file of the index build
         map_path = a.pq_cluster_path.replace("clus", "mapping")
         # every rank looks BEFORE anyone writes (barrier), so all ranks take the same branch and the barriers below pair
         # up: a rank arriving after rank 0 had written the pickles used to skip rank 0's barrier (one-off from then on)

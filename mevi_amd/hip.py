@@ -237,6 +237,13 @@ _OPQ_SIGNATURES = {
 }
 
 
+# include/mevi_hip_opq_encode.h (included by mevi_hip.h): rotate + product-quantiser encode in one launch (ProductQuantization('opq'))
+_OPQ_ENCODE_SIGNATURES = {
+    "mevi_opq_encode_fused": (c_int, [c_int64] * 4),
+    "mevi_opq_encode_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+}
+
+
 # include/mevi_hip_refine.h (included by mevi_hip.h): exact re-ranking of the candidate ids a compressed index returned
 _REFINE_SIGNATURES = {
     "mevi_refine_topk_workspace_bytes": (c_size_t, [c_int64] * 4),
@@ -308,12 +315,12 @@ def attn_route_name(route):
 
 def exported_symbols(header="mevi_hip.h"):
     """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h /
-    mevi_hip_ivfpq.h / mevi_hip_pqfs.h / mevi_hip_sq.h / mevi_hip_opq.h / mevi_hip_graph.h / mevi_hip_graph_levels.h /
+    mevi_hip_ivfpq.h / mevi_hip_pqfs.h / mevi_hip_sq.h / mevi_hip_opq.h / mevi_hip_opq_encode.h / mevi_hip_graph.h / mevi_hip_graph_levels.h /
     mevi_hip_refine.h / mevi_hip_aq.h, which it includes)."""
     return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES, "mevi_hip_refine.h": _REFINE_SIGNATURES,
                    "mevi_hip_aq.h": _AQ_SIGNATURES,
                    "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES, "mevi_hip_sq.h": _SQ_SIGNATURES,
-                   "mevi_hip_pqfs.h": _PQFS_SIGNATURES, "mevi_hip_opq.h": _OPQ_SIGNATURES, "mevi_hip_graph.h": _GRAPH_SIGNATURES, "mevi_hip_graph_levels.h": _GRAPH_LEVELS_SIGNATURES}[header])
+                   "mevi_hip_pqfs.h": _PQFS_SIGNATURES, "mevi_hip_opq.h": _OPQ_SIGNATURES, "mevi_hip_opq_encode.h": _OPQ_ENCODE_SIGNATURES, "mevi_hip_graph.h": _GRAPH_SIGNATURES, "mevi_hip_graph_levels.h": _GRAPH_LEVELS_SIGNATURES}[header])
 
 
 def lib():
@@ -325,7 +332,7 @@ def lib():
                 "(or __graft_entry__.build()); mevi_amd has no CPU fallback")
         L = ctypes.CDLL(LIB)
         for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES,
-                                  **_PQFS_SIGNATURES, **_SQ_SIGNATURES, **_OPQ_SIGNATURES, **_GRAPH_SIGNATURES, **_GRAPH_LEVELS_SIGNATURES,
+                                  **_PQFS_SIGNATURES, **_SQ_SIGNATURES, **_OPQ_SIGNATURES, **_OPQ_ENCODE_SIGNATURES, **_GRAPH_SIGNATURES, **_GRAPH_LEVELS_SIGNATURES,
                                   **_REFINE_SIGNATURES, **_AQ_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res

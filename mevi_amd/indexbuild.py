@@ -6,7 +6,9 @@ from the reference.  Mirrors on_validation_epoch_start of the re
   1. gen_doc_embedding (:3077-3180)   docemb.bin, unless it exists: every rank encodes rows // nrank passages (the last
                                       rank takes the rest) into `<prefix>_<rank>.bin`, rank 0 concatenates
   2. pq.initialize (pq.py:440-486)    rqcodebook*.pt, unless it exists: k-means on the embeddings (rank 0) -- per residual
-                                      level (--pq_type rq) or per column slice (--pq_type pq)
+                                      level (--pq_type rq) or per column slice (--pq_type pq); --pq_type opq (with
+                                      --pq_init_method faiss): the OPQ rotation, then per-slice k-means on a rotated sample,
+                                      saved together as {"codebook", "rotate"}
   3. gen_pq_doc_cluster (:3182-3220)  rqclus*.pkl / rqmapping*.pkl, unless they exist
 
 Host side only: the device work is TwinTower / BertTower, mevi_amd.rq (k-means, RQ / PQ encode)."""
@@ -119,8 +121,16 @@ def build_index(args, rank=0, nrank=1, barrier=None, device=None, tower=None, to
     pq_file = args.pq_path if args.pq_path and os.path.isfile(args.pq_path) else None
     if dim is None:
         if pq_file is not None:   # rq: [M, K, dim]; pq: [M, K, dim // M]
-            shape = torch.load(pq_file, map_location="cpu").shape
-            dim = int(shape[-1]) * (int(shape[0]) if pq_type == "pq" else 1)
+            obj = torch.load(pq_file, map_location="cpu")
+            if pq_type == "opq":  # {"codebook": [M, K, dim // M], "rotate": [dim, dim]} (ProductQuantization.load_opq_file)
+                if not isinstance(obj, dict) or "rotate" not in obj:
+                    raise SystemExit(f"--pq_type opq: {pq_file} holds no rotation (a torch.save of {{'codebook', 'rotate'}} "
+                                     "is expected; a bare codebook tensor or a faiss index is not an opq file)")
+                dim = int(obj["rotate"].shape[0])
+            else:
+                shape = obj.shape
+                dim = int(shape[-1]) * (int(shape[0]) if pq_type == "pq" else 1)
+            del obj
         else:
             tower = tower or load_tower(args, device)
             dim = tower.dim

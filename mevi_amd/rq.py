@@ -11,8 +11,10 @@ Reference surface mirrored (same names and argument meaning):
     .forward(vecs) -> index   (forward_rq, pq.py:337-369; proba/loss are training outputs)
     .get_reconstruct_vector(index)                            pq.py:768-784
 'pq' differs from 'rq' only in the coding: subspace j of a row (columns j*dsub .. (j+1)*dsub - 1, dsub = dim // M) is
-coded against C[j] alone, reconstruct = concatenation.  EMA / gumbel training, 'opq' and 'ip' / 'iptol2' are out of
-scope.
+coded against C[j] alone, reconstruct = concatenation.  'opq' is 'pq' behind a rotation (pq.py:67-71, 259-279, 629-630, 775-783):
+`rotate` f32[dim, dim] beside the codebook, y = x @ rotate.T is what gets coded (mevi_opq_encode_f32: rotate + encode in one launch),
+reconstruct = concatenation @ rotate; its training stands in for the reference's faiss branch (`train_opq`).  EMA / gumbel training
+and 'ip' / 'iptol2' are out of scope.
 """
 from collections import defaultdict
 
@@ -96,6 +98,45 @@ def pq_encode(x, codebook):
         st = hip.lib().mevi_pq_encode_f32(hip.ptr(x), n, dim, hip.ptr(codebook), M, K, dsub, hip.ptr(codes),
                                           hip.stream_ptr())
     hip.check(st, "mevi_pq_encode_f32")
+    return codes
+
+
+OPQ_ENCODE_DEFAULT = "fused"      # MEVI_OPQ_ENCODE: 'fused' = mevi_opq_encode_f32, 'steps' = rotate a chunk, then mevi_pq_encode_f32
+
+
+def opq_encode(x, R, codebook, mode=None):
+    """codes i32[n, M] of chain(x, R) f32[n, dim] against a product codebook f32[M, K, dsub], M * dsub == dim (CUDA tensors): the
+    codes `pq_encode` gives for the rows rotated by mevi_opq_rotate_rows_f32, bit for bit.
+    mode (default MEVI_OPQ_ENCODE or OPQ_ENCODE_DEFAULT): 'fused' = mevi_opq_encode_f32 (csrc/opq_encode.hip), one launch, no rotated
+    value reaches memory; 'steps' = that composition, `ivfpq.ENCODE_CHUNK` rows rotated at a time.  A shape outside the fused
+    kernel's envelope (mevi_opq_encode_fused) takes 'steps' whatever the mode."""
+    import os
+
+    hip.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+    assert R.is_cuda and R.dtype == torch.float32 and codebook.is_cuda and codebook.dtype == torch.float32
+    x, R, codebook = x.contiguous(), R.contiguous(), codebook.contiguous()
+    M, K, dsub = codebook.shape
+    n, dim = x.shape
+    assert M * dsub == dim and tuple(R.shape) == (dim, dim), (x.shape, R.shape, codebook.shape)
+    mode = mode or os.environ.get("MEVI_OPQ_ENCODE", OPQ_ENCODE_DEFAULT)
+    if mode not in ("fused", "steps"):
+        raise ValueError(f"MEVI_OPQ_ENCODE={mode!r} is neither 'fused' nor 'steps'")
+    L = hip.lib()
+    if mode == "fused" and L.mevi_opq_encode_fused(dim, M, K, dsub):
+        codes = torch.empty((n, M), dtype=torch.int32, device=x.device)
+        with hip.device_guard(x.device):
+            st = L.mevi_opq_encode_f32(hip.ptr(x) if n else None, n, dim, hip.ptr(R), hip.ptr(codebook), M, K, dsub,
+                                       hip.ptr(codes) if n else None, hip.stream_ptr())
+        hip.check(st, "mevi_opq_encode_f32")
+        return codes
+    from . import dense
+    from .ivfpq import ENCODE_CHUNK
+
+    codes = torch.empty((n, M), dtype=torch.int32, device=x.device)
+    for a in range(0, n, ENCODE_CHUNK):       # the rotated chunk is the only rotated rows that exist
+        y = dense.opq_rotate_rows(x[a:a + ENCODE_CHUNK], None, None, None, R, mode="fused")
+        codes[a:a + ENCODE_CHUNK] = pq_encode(y, codebook)
     return codes
 
 
@@ -354,8 +395,11 @@ class ClusterIndex:
 class ProductQuantization:
     def __init__(self, pq_type="rq", subvector_num=4, subvector_bits=5, dist_mode="l2", emb_size=768,
                  pq_init_method="kmeans", pq_update_method="none", device=None, **unused):
-        if pq_type not in ("rq", "pq") or dist_mode != "l2":
-            raise NotImplementedError("only pq_type 'rq' or 'pq' with dist_mode='l2' is on the MEVI eval path")
+        if pq_type not in ("rq", "pq", "opq") or dist_mode != "l2":
+            raise NotImplementedError("only pq_type 'rq', 'pq' or 'opq' with dist_mode='l2' is on the MEVI eval path")
+        if pq_type == "opq" and (subvector_num < 1 or emb_size % subvector_num != 0 or (emb_size // subvector_num) % 4 != 0):
+            raise NotImplementedError(f"pq_type 'opq': emb_size={emb_size} does not split into subvector_num={subvector_num} "
+                                      "slices of a multiple of 4 columns")
         self.pq_type, self.dist_mode = pq_type, dist_mode
         self.subvector_num, self.subvector_bits = subvector_num, subvector_bits
         self.subvector_cents = 2 ** subvector_bits
@@ -365,6 +409,8 @@ class ProductQuantization:
         self.device = torch.device(device if device is not None else "cuda")
         self.codebook = torch.empty((subvector_num, self.subvector_cents, self.last_dim), dtype=torch.float32,
                                     device=self.device)
+        # 'opq' (pq.py:67-71): y = x @ rotate.T is what the product quantiser codes; reconstruct rotates back
+        self.rotate = torch.eye(emb_size, dtype=torch.float32, device=self.device) if pq_type == "opq" else None
 
     def get_codebook(self):
         return self.codebook
@@ -377,9 +423,25 @@ class ProductQuantization:
         assert tuple(t.shape) == tuple(self.codebook.shape), (t.shape, self.codebook.shape)
         self.codebook.copy_(t.to(self.device))
 
+    def load_rotation(self, tensor):
+        assert self.pq_type == "opq", self.pq_type
+        t = torch.as_tensor(np.asarray(tensor) if not torch.is_tensor(tensor) else tensor.detach(), dtype=torch.float32)
+        assert tuple(t.shape) == tuple(self.rotate.shape), (t.shape, self.rotate.shape)
+        self.rotate.copy_(t.to(self.device))
+
+    def load_opq_file(self, obj, where="the opq file"):
+        """The 'opq' form of `pq_path`: torch.save({"codebook": f32[M, K, dsub], "rotate": f32[dim, dim]}) -- this build's own
+        format (the reference reads the pair out of a faiss index file, pq.py:143-173, which cannot be read here)."""
+        if not isinstance(obj, dict) or "codebook" not in obj or "rotate" not in obj:
+            raise ValueError(f"pq_type 'opq': {where} must be a torch.save of {{'codebook': f32[M, K, dim // M], 'rotate': "
+                             f"f32[dim, dim]}}; a bare {type(obj).__name__} has no rotation (a 'pq' / 'rq' codebook file, or a "
+                             "faiss index, is not an opq file)")
+        self.load_codebook(obj["codebook"])
+        self.load_rotation(obj["rotate"])
+
     def initialize(self, index_file, doc_emb=None, rank=0, seed=0, pq_cluster_path=None, encode_batch_size=None):
-        """Rank 0 loads `rqcodebook{M}_{bits}.pt` (torch.save of the f32[M,K,dim] parameter; f32[M,K,dim//M] for 'pq'),
-        then the codebook is broadcast (RCCL) when a process group exists."""
+        """Rank 0 loads `rqcodebook{M}_{bits}.pt` (torch.save of the f32[M,K,dim] parameter; f32[M,K,dim//M] for 'pq'; the
+        {"codebook", "rotate"} dict of `load_opq_file` for 'opq'), then the state is broadcast (RCCL) when a process group exists."""
         import os
 
         import torch.distributed as dist
@@ -387,21 +449,54 @@ class ProductQuantization:
         if rank == 0:
             if index_file is not None and os.path.isfile(index_file):
                 print("Intializing codebook with torch file...")
-                self.load_codebook(torch.load(index_file, map_location="cpu"))
+                obj = torch.load(index_file, map_location="cpu")
+                if self.pq_type == "opq":
+                    self.load_opq_file(obj, index_file)
+                else:
+                    self.load_codebook(obj)
             elif doc_emb is not None:  # pq.py:402-419: no file -> train on the embeddings, then save next to it
-                self.unsupervised_update_codebook_manually(doc_emb, seed, self.pq_init_method)
+                if self.pq_type == "opq":
+                    self.train_opq(doc_emb, seed)
+                else:
+                    self.unsupervised_update_codebook_manually(doc_emb, seed, self.pq_init_method)
                 if index_file is not None:
-                    torch.save(self.codebook.detach().cpu(), index_file)
+                    torch.save({"codebook": self.codebook.detach().cpu(), "rotate": self.rotate.detach().cpu()}
+                               if self.pq_type == "opq" else self.codebook.detach().cpu(), index_file)
             else:
                 raise FileNotFoundError(f"{self.pq_type.upper()} codebook {index_file} not found and no embeddings to train one on")
         if dist.is_available() and dist.is_initialized():
             dist.broadcast(self.codebook, 0)
+            if self.rotate is not None:
+                dist.broadcast(self.rotate, 0)
+
+    def train_opq(self, doc_emb, seed):
+        """What faiss trains for 'OPQ{M},PQ{M}x{bits}' (the reference's pq_init_method 'faiss', pq.py:455-458, :182): the
+        OPQMatrix rotation (`opq.train_rotation`, on the device), then the product quantiser on the rotated training sample of at
+        most 256 * K rows (`ivfpq.train_codebook`'s sample and k-means settings).  That sample is the only rotated rows that exist."""
+        from . import dense, ivfpq, opq
+
+        x = doc_emb if torch.is_tensor(doc_emb) else torch.from_numpy(np.ascontiguousarray(doc_emb, dtype=np.float32))
+        x = x.to(self.device, torch.float32).contiguous()
+        M, K = self.subvector_num, self.subvector_cents
+        if x.shape[0] < opq.TRAIN_K:
+            raise ValueError(f"pq_type 'opq': the rotation trainer needs at least {opq.TRAIN_K} rows, got {x.shape[0]}")
+        print("Training the OPQ rotation and its product codebook...")
+        with hip.device_guard(self.device):
+            R, errors = opq.train_rotation(x, M, seed=int(seed))
+            gen = torch.Generator(device=x.device).manual_seed(int(seed))
+            n = x.shape[0]
+            rows = torch.randperm(n, generator=gen, device=x.device)[:min(n, ivfpq.MAX_POINTS_PER_CENTROID * K)]
+            ys = dense.opq_rotate_rows(x, rows, None, None, R.contiguous(), mode="fused")
+            book = train_pq_codebook(ys, M, K, seed=int(seed), n_init=1, max_iter=ivfpq.PQ_NITER)[0]
+        self.rotate.copy_(R)
+        self.codebook.copy_(book)
+        print(f"OPQ rotation: niter {len(errors)}, training error {errors[0]:.6g} -> {errors[-1]:.6g}; {dict(opq.LAST_TRAIN)}")
 
     def unsupervised_update_codebook_manually(self, doc_emb, seed, kmeans_method="kmeans"):
         """Train the codebook on `doc_emb` (MEVI/pq.py:550-598, the scikit-learn path): 'rq' level i = k-means
         (k = 2**bits) on the residual of levels < i, 'pq' subspace j = k-means on column slice j.  Runs on the GPU
         (`train_rq_codebook` / `train_pq_codebook`); sets `last_preds` (i64 ndarray [n, M]) like the reference."""
-        assert kmeans_method == "kmeans", kmeans_method
+        assert kmeans_method == "kmeans" and self.pq_type != "opq", (kmeans_method, self.pq_type)      # pq.py:553
         print("Updating codebook using KMeans...")
         x = doc_emb if torch.is_tensor(doc_emb) else torch.from_numpy(np.ascontiguousarray(doc_emb, dtype=np.float32))
         x = x.to(self.device, torch.float32)
@@ -411,7 +506,18 @@ class ProductQuantization:
         self.last_preds = codes.cpu().numpy().astype(np.int64)
 
     def _encode(self, x):
+        if self.pq_type == "opq":
+            return opq_encode(x, self.rotate, self.codebook)
         return rq_encode(x, self.codebook) if self.pq_type == "rq" else pq_encode(x, self.codebook)
+
+    def _rotated(self, doc_emb):
+        """f32 [bs, dim] on the device: the rows the 'pq' beam encode scores -- chain(x, rotate) under 'opq' (pq.py:629-630)."""
+        x = doc_emb.to(self.device, torch.float32).contiguous()
+        if self.pq_type != "opq" or x.shape[0] == 0:
+            return x
+        from . import dense
+
+        return dense.opq_rotate_rows(x, None, None, None, self.rotate, mode="fused")
 
     def forward(self, vecs, return_loss=False):
         """index i32[n, M]; the reference's (proba, index, loss) triple minus the training outputs."""
@@ -466,12 +572,12 @@ class ProductQuantization:
         mode = os.environ.get("MEVI_RQ_BEAM", "fused")
         assert mode in ("fused", "steps"), mode
         return mode == "fused" and hip.lib().mevi_rq_beam_encode_tile_docs(
-            self.emb_size, self.subvector_num, self.subvector_cents, num_return_sequences, int(self.pq_type == "pq")) > 0
+            self.emb_size, self.subvector_num, self.subvector_cents, num_return_sequences, int(self.pq_type != "rq")) > 0
 
     def _beam_workspace(self, n, R):
         """The fused call's workspace, cached per (device, stream, shape): its size does not depend on n, and calls on one
         stream run one after the other, so they can share the tile ticket it holds."""
-        pq = int(self.pq_type == "pq")
+        pq = int(self.pq_type != "rq")
         key = (self.device, hip.stream_ptr(), self.emb_size, self.subvector_num, self.subvector_cents, R, pq)
         ws = _BEAM_WORKSPACES.get(key)
         if ws is None:
@@ -482,7 +588,7 @@ class ProductQuantization:
     def _beam_search_fused(self, doc_emb, num_return_sequences, return_proba):
         """All levels in one launch: reads x once, writes labels and probabilities only."""
         R, M, K = num_return_sequences, self.subvector_num, self.subvector_cents
-        x = doc_emb.to(self.device, torch.float32).contiguous()
+        x = self._rotated(doc_emb)
         assert x.dim() == 2 and x.shape[1] == self.emb_size, (x.shape, self.emb_size)
         bs = x.shape[0]
         labels = torch.empty((bs, R, M), dtype=torch.int32, device=self.device)
@@ -491,7 +597,7 @@ class ProductQuantization:
             return (labels, proba) if return_proba else labels
         ws = self._beam_workspace(bs, R)
         st = hip.lib().mevi_rq_beam_encode_f32(hip.ptr(x), bs, self.emb_size, hip.ptr(self.codebook), M, K, R,
-                                               int(self.pq_type == "pq"), hip.ptr(labels), None if proba is None else hip.ptr(proba),
+                                               int(self.pq_type != "rq"), hip.ptr(labels), None if proba is None else hip.ptr(proba),
                                                hip.ptr(ws), ws.numel(), hip.stream_ptr())
         hip.check(st, "mevi_rq_beam_encode_f32")
         return (labels, proba) if return_proba else labels
@@ -500,8 +606,8 @@ class ProductQuantization:
         """The per-level composition (MEVI_RQ_BEAM=steps, and every shape outside the fused call's envelope)."""
         L = hip.lib()
         R, M, K, dim = num_return_sequences, self.subvector_num, self.subvector_cents, self.last_dim
-        pq = self.pq_type == "pq"
-        x = doc_emb.to(self.device, torch.float32).contiguous()
+        pq = self.pq_type != "rq"
+        x = self._rotated(doc_emb)
         bs = x.shape[0]
         resid, nb = x, 1
         scores = torch.ones((bs, 1), dtype=torch.float32, device=self.device)
@@ -547,8 +653,13 @@ class ProductQuantization:
         n = doc_embeddings.shape[0]
         per = n // nrank
         start, end = per * rank, n if rank + 1 == nrank else per * (rank + 1)
-        if torch.is_tensor(doc_embeddings) and doc_embeddings.is_cuda and self.beam_search_is_fused(num_return_sequences):
+        on_device = torch.is_tensor(doc_embeddings) and doc_embeddings.is_cuda
+        if on_device and self.pq_type != "opq" and self.beam_search_is_fused(num_return_sequences):
             return self.beam_search(doc_embeddings[start:end], num_return_sequences).cpu()   # one call, one copy back
+        if self.pq_type == "opq":      # a chunk is rotated at a time: no second copy of the corpus exists
+            from .ivfpq import ENCODE_CHUNK
+
+            batch_size = ENCODE_CHUNK if on_device else min(batch_size, ENCODE_CHUNK)
         out = torch.empty((end - start, num_return_sequences, self.subvector_num), dtype=torch.int32)
         for s in range(start, end, batch_size):
             e = min(s + batch_size, end)
@@ -564,6 +675,12 @@ class ProductQuantization:
         index = index.to(cb.device).long()
         if self.pq_type == "pq":
             return torch.cat([cb[j][index[..., j]] for j in range(cb.shape[0])], dim=-1)
+        if self.pq_type == "opq":      # pq.py:775-783: the concatenation, rotated back into the input space (vectors @ rotate)
+            from . import ops
+
+            vectors = torch.cat([cb[j][index[..., j]] for j in range(cb.shape[0])], dim=-1)
+            flat = ops.linear(vectors.reshape(-1, vectors.shape[-1]).contiguous(), self.rotate.t().contiguous())
+            return flat.reshape(vectors.shape)
         out = torch.zeros(index.shape[:-1] + (cb.shape[-1],), dtype=torch.float32, device=cb.device)
         for j in range(cb.shape[0]):
             out = out + cb[j][index[..., j]]

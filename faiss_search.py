@@ -19,7 +19,7 @@ deterministic upper levels instead of scanning strided entry rows; MEVI_HNSW=exa
 the device (mevi_amd/sq.py; same nprobe and recall report; MEVI_SQ=exact or a shape outside the index's envelope gives the exact
 search instead); "RQ<M>x<b>" and "IVF<n>,RQ<M>x<b>" (b <= 8) build a residual quantiser -- M code bytes a row as "PQ<M>", every
 code a full-width centroid of what the levels before it leave -- searched by ADC with full-width lookup tables (mevi_amd/rqindex.py;
-greedy encoding and training where faiss keeps a beam of 5; the report adds the training error per level; MEVI_RQINDEX=exact, a
+greedy encoding and training where faiss keeps a beam of 5, unless MEVI_RQINDEX_BEAM / MEVI_RQINDEX_TRAIN_BEAM = 1..16 ask for one; the report adds the training error per level; MEVI_RQINDEX=exact, a
 shape outside the envelope, "RQ<M>" without a width, norm suffixes, "LSQ..." and "PRQ..." give the exact search instead; not sharded
 under torchrun); "<index>,RFlat" and "<index>,Refine(Flat)" behind any of the PQ, x4fs, OPQ, SQ and RQ strings above ask that index
 for int(topk * MEVI_REFINE_K_FACTOR) candidates (default factor 1, as faiss) and re-rank them against the original rows on the

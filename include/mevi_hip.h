@@ -304,6 +304,11 @@ int mevi_fine_topk_f32(const float *q, int64_t ldq, int per_beam, int64_t nq, in
  * mevi_hip_aq.h. */
 #include "mevi_hip_aq.h"
 
+/* The beam-search encoder of those indexes (faiss max_beam_size): one level's step -- B residual rows per document against K
+ * centroids, the L extensions of smallest reconstruction error kept in order, their residual rows written -- with its two sizing
+ * functions, and the backtrack from the levels' traces to code rows, declared and documented in mevi_hip_rq_errbeam.h. */
+#include "mevi_hip_rq_errbeam.h"
+
 /* ------------------------------------------------------------------------
  * Residual-quantisation encode: codes[n, M] (int32, values in [0, K)).
  * Replaces pq.get_rq_document_cluster / the index path of forward_rq with

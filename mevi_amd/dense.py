@@ -359,6 +359,71 @@ def rq_residual(x, codebook, codes, out=None):
     return out
 
 
+def rq_errbeam_step_workspace_bytes(n, dim, K, B, L):
+    """Bytes of workspace `rq_errbeam_step` needs (host arithmetic, independent of n; 0 = outside the kernel's envelope)."""
+    return int(hip.lib().mevi_rq_errbeam_step_workspace_bytes(n, dim, K, B, L))
+
+
+def rq_errbeam_step_tile_docs(dim, K, B, L):
+    """Documents a workgroup of `rq_errbeam_step` draws per ticket (0 = outside the envelope)."""
+    return int(hip.lib().mevi_rq_errbeam_step_tile_docs(dim, K, B, L))
+
+
+def rq_errbeam_step(res_in, centroids, L, res_out=None, want_res=True, workspace=None):
+    """One level of the residual quantiser's beam-search encoder (mevi_rq_errbeam_step_f32): res_in f32 [n, B, dim], the B residual
+    rows of every document; centroids f32 [K, dim].  -> (parent u8 [n, Lo], code u8 [n, Lo], err f32 [n, Lo], res_out f32
+    [n, Lo, dim] or None), Lo = min(L, B * K): the Lo extensions of smallest reconstruction error in ascending (err, b * K + c)
+    order and, unless `want_res` is False (the last level), their residual rows res_in[parent] - centroids[code].  `res_out` may
+    be given (it must not overlap res_in); with it and `workspace` (uint8, rq_errbeam_step_workspace_bytes) only the three small
+    outputs are allocated.  Stream-ordered."""
+    hip.require_gpu()
+    assert res_in.is_cuda and res_in.dtype == torch.float32 and res_in.dim() == 3 and res_in.is_contiguous()
+    assert centroids.is_cuda and centroids.dtype == torch.float32 and centroids.dim() == 2 and centroids.is_contiguous()
+    n, B, dim = res_in.shape
+    K = centroids.shape[0]
+    assert centroids.shape[1] == dim and B >= 1 and K >= 1
+    Lo = min(int(L), B * K)
+    dev = res_in.device
+    parent = torch.empty((n, Lo), dtype=torch.uint8, device=dev)
+    code = torch.empty((n, Lo), dtype=torch.uint8, device=dev)
+    err = torch.empty((n, Lo), dtype=torch.float32, device=dev)
+    if not want_res:
+        res_out = None
+    elif res_out is None:
+        res_out = torch.empty((n, Lo, dim), dtype=torch.float32, device=dev)
+    else:
+        assert res_out.shape == (n, Lo, dim) and res_out.dtype == torch.float32 and res_out.is_contiguous() and res_out.is_cuda
+    if workspace is None:
+        workspace = torch.empty(max(1, rq_errbeam_step_workspace_bytes(n, dim, K, B, L)), dtype=torch.uint8, device=dev)
+    with hip.device_guard(dev):
+        # (an empty tensor has no address to hand over: the centroids stand in, nothing is read)
+        st = hip.lib().mevi_rq_errbeam_step_f32(hip.ptr(res_in) if n else hip.ptr(centroids), n, B, dim, hip.ptr(centroids), K, L,
+                                                hip.ptr(parent) if n else hip.ptr(workspace), hip.ptr(code) if n else hip.ptr(workspace),
+                                                hip.ptr(err) if n else None, hip.ptr(res_out) if n and res_out is not None else None,
+                                                hip.ptr(workspace), workspace.numel(), hip.stream_ptr())
+    hip.check(st, "mevi_rq_errbeam_step_f32")
+    return parent, code, err, res_out
+
+
+def rq_errbeam_codes(parent, code, n, out=None):
+    """u8 [n, M]: the code rows of slot 0's paths (mevi_rq_errbeam_codes_u8) from the traces parent / code u8 [M, n, S] of M steps
+    (level j's step wrote its [n, Lo_j] into [j, :, :Lo_j]).  `out` u8 [n, >= M] with any row stride is written in place."""
+    hip.require_gpu()
+    assert parent.is_cuda and parent.dtype == torch.uint8 and parent.dim() == 3 and parent.is_contiguous()
+    assert code.is_cuda and code.dtype == torch.uint8 and code.shape == parent.shape and code.is_contiguous()
+    M, rows, S = parent.shape
+    assert rows == n and M >= 1 and S >= 1
+    if out is None:
+        out = torch.empty((n, M), dtype=torch.uint8, device=parent.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n and out.shape[1] >= M
+    assert n == 0 or out.stride(1) == 1
+    with hip.device_guard(parent.device):
+        st = hip.lib().mevi_rq_errbeam_codes_u8(hip.ptr(parent) if n else None, hip.ptr(code) if n else None, M, n, S,
+                                                hip.ptr(out) if n else None, out.stride(0) if n else M, hip.stream_ptr())
+    hip.check(st, "mevi_rq_errbeam_codes_u8")
+    return out
+
+
 PQFS_ROW_BLOCK = 2048               # MEVI_PQFS_SCAN_ROW_BLOCK: rows of a list per work item of the packed 4-bit ADC scan
 PQFS_MIN_M, PQFS_MAX_M = 8, 96      # subspaces (nibbles per row) that scan takes; m % 8 == 0
 
@@ -1044,7 +1109,7 @@ def search(query, doc, dim, topk, param="Flat", device=None):
     dim / M % 4 != 0, fewer than 256 rows, an inner index outside its own envelope and OPQ in front of anything else);
     "RQ<M>x<b>" / "IVF<n>,RQ<M>x<b>" (b <= 8) -> a residual quantiser: M code bytes a row as "PQ<M>", every code a full-width
     centroid of what the levels before it leave, searched by ADC with full-width lookup tables (mevi_amd/rqindex.py; greedy
-    encoding and training where faiss keeps a beam of 5; same nprobe and recall report, plus the training error per level;
+    encoding and training where faiss keeps a beam of 5, unless MEVI_RQINDEX_BEAM / MEVI_RQINDEX_TRAIN_BEAM = 1..16 ask for one; same nprobe and recall report, plus the training error per level;
     MEVI_RQINDEX=exact answers them with the exact search instead, as do dim % 4 != 0, M % 4 != 0, M outside 4..96, M * 2^b * 4
     bytes above 96 KiB, fewer rows than 2^b, nlist > rows, topk > 4096, and the strings "RQ<M>" without a width, "RQ..._N<norm>",
     "RQ1x16-6x8", "LSQ...", "PRQ..." and "OPQ...,RQ...");

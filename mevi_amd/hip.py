@@ -264,6 +264,16 @@ _AQ_SIGNATURES = {
 }
 
 
+# include/mevi_hip_rq_errbeam.h (included by mevi_hip.h): one level of the residual quantiser's beam-search encoder, and its backtrack
+_RQ_ERRBEAM_SIGNATURES = {
+    "mevi_rq_errbeam_step_workspace_bytes": (c_size_t, [c_int64] * 5),
+    "mevi_rq_errbeam_step_tile_docs": (c_int64, [c_int64] * 4),
+    "mevi_rq_errbeam_step_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mevi_rq_errbeam_codes_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+}
+
+
 # include/mevi_hip_graph.h (included by mevi_hip.h): the neighbour graph of "HNSW<M>", its linking and its search
 _GRAPH_SIGNATURES = {
     "mevi_graph_link_workspace_bytes": (c_size_t, [c_int64] * 3),
@@ -316,9 +326,9 @@ def attn_route_name(route):
 def exported_symbols(header="mevi_hip.h"):
     """Names every entry point the text of include/<header> declares (mevi_hip.h, or mevi_hip_fine_agg.h / mevi_hip_attn_long.h /
     mevi_hip_ivfpq.h / mevi_hip_pqfs.h / mevi_hip_sq.h / mevi_hip_opq.h / mevi_hip_opq_encode.h / mevi_hip_graph.h / mevi_hip_graph_levels.h /
-    mevi_hip_refine.h / mevi_hip_aq.h, which it includes)."""
+    mevi_hip_refine.h / mevi_hip_aq.h / mevi_hip_rq_errbeam.h, which it includes)."""
     return sorted({"mevi_hip.h": _SIGNATURES, "mevi_hip_fine_agg.h": _FINE_AGG_SIGNATURES, "mevi_hip_refine.h": _REFINE_SIGNATURES,
-                   "mevi_hip_aq.h": _AQ_SIGNATURES,
+                   "mevi_hip_aq.h": _AQ_SIGNATURES, "mevi_hip_rq_errbeam.h": _RQ_ERRBEAM_SIGNATURES,
                    "mevi_hip_attn_long.h": _ATTN_LONG_SIGNATURES, "mevi_hip_ivfpq.h": _IVFPQ_SIGNATURES, "mevi_hip_sq.h": _SQ_SIGNATURES,
                    "mevi_hip_pqfs.h": _PQFS_SIGNATURES, "mevi_hip_opq.h": _OPQ_SIGNATURES, "mevi_hip_opq_encode.h": _OPQ_ENCODE_SIGNATURES, "mevi_hip_graph.h": _GRAPH_SIGNATURES, "mevi_hip_graph_levels.h": _GRAPH_LEVELS_SIGNATURES}[header])
 
@@ -333,7 +343,7 @@ def lib():
         L = ctypes.CDLL(LIB)
         for name, (res, args) in {**_SIGNATURES, **_FINE_AGG_SIGNATURES, **_ATTN_LONG_SIGNATURES, **_IVFPQ_SIGNATURES,
                                   **_PQFS_SIGNATURES, **_SQ_SIGNATURES, **_OPQ_SIGNATURES, **_OPQ_ENCODE_SIGNATURES, **_GRAPH_SIGNATURES, **_GRAPH_LEVELS_SIGNATURES,
-                                  **_REFINE_SIGNATURES, **_AQ_SIGNATURES}.items():
+                                  **_REFINE_SIGNATURES, **_AQ_SIGNATURES, **_RQ_ERRBEAM_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -7,10 +7,12 @@ the coarse centroid behind IVF), a document is stored as its M code bytes -- 64 
 and a search scores the rows of the query's `nprobe` best lists by ADC: <q, centroid> + sum_j <q, codebook[j][code_j]>.  `RQ{M}x{b}`
 is the string the reference's own codebook builder hands to faiss (MEVI/pq.py:183-184).
 
-Two deliberate deviations from faiss:
-  * encoding and training are GREEDY: level i takes the nearest centroid to the residual of levels < i.  faiss keeps a beam
-    (`max_beam_size` = 5) through the levels in both.  The fused beam encoder of this project (mevi_rq_beam_encode_f32) stops at 8
-    levels, and a beam across groups of levels is not built;
+Two deliberate deviations from faiss, the first one a default only:
+  * encoding and training are GREEDY by default: level i takes the nearest centroid to the residual of levels < i.  faiss keeps a
+    beam (`max_beam_size` = 5) through the levels in both.  `RQIndex(..., beam=L)` / MEVI_RQINDEX_BEAM=L (1..16; faiss: 5) encodes
+    with a beam of L paths ranked by reconstruction error (below); MEVI_RQINDEX_TRAIN_BEAM=L trains every level on the residuals
+    of all beam entries, as faiss's trainer does.  Both default to 1, which is the greedy code path, untouched.  (The fused beam
+    encoder mevi_rq_beam_encode_f32 is MEVI's cluster beam: softmax products, 8 levels -- it is not this one.);
   * k-means is seeded from our own RNG, as for every index here, so centroids and codebooks cannot be compared with faiss.
 What IS defined -- and tested bit for bit against the oracle -- given the centroids and the codebook:
   * the list of a row: `ivf.assign` (largest inner product, lowest list on ties);
@@ -20,10 +22,17 @@ What IS defined -- and tested bit for bit against the oracle -- given the centro
   * search: lut[j][c] = the sequential fmaf chain <q, codebook[j][c]> from +0 over all dim columns, score = ((bias + lut[0][code_0])
     + lut[1][code_1]) + ... in ascending j with bias = the coarse score of the list (+0 without a coarse quantiser), top-k over all
     probed rows (score desc, id asc, -FLT_MAX / -1 padding).
+Beam encoding (beam = L > 1), defined level by level and tested bit for bit (tests/rq_errbeam_cases.py): a level takes the B residual
+rows a document has (1 at level 0: the row `encode` forms today), err(b, c) = the fmaf chain of the squared differences to centroid
+c (the bits of -mevi_rq_neg_dist_f32: the whole reconstruction error of that path), keeps the min(L, B * K) smallest (err, b * K + c)
+in ascending order and hands on res[parent] - centroid[code]; the stored codes are the path of slot 0 after the last level.  With
+L = 1 that walk IS the greedy encoder.  One mevi_rq_errbeam_step_f32 per level over ping-pong buffers, one mevi_rq_errbeam_codes_u8
+per chunk; MEVI_RQINDEX_BEAM_STEP=steps (and dim > 4096) runs a level as mevi_rq_neg_dist_f32 -> torch.sort of the packed keys ->
+mevi_gather_sub_f32 instead.  The search side is the same bytes, tables and scan.
 `RQIndex.search` is two stream-ordered device calls, the coarse quantiser of IVF-PQ (mevi_ivf_scan_topk_f32 on the centroids as one
 list) and mevi_aq_scan_topk_f32 (csrc/aq_scan.hip); up to GRAPH_MAX_QUERIES queries can be captured and replayed (`search_graph`).
 
-Not built: beam encoding, norm suffixes ('RQ8x8_Nqint8', ... -- they store a norm for L2 search; inner product needs none), 'LSQ...'
+Not built: norm suffixes ('RQ8x8_Nqint8', ... -- they store a norm for L2 search; inner product needs none), 'LSQ...'
 and 'PRQ...' (local-search and product-residual quantisers), groups of levels of different widths ('RQ1x16-6x8'), 'OPQ...,RQ...',
 a sharded form under torchrun.  Those strings keep the exact search, as do MEVI_RQINDEX=exact and shapes outside the envelope.
 """
@@ -40,6 +49,23 @@ RQ_NITER = 25                     # ... and every level's k-means runs 25 iterat
 GRAPH_MAX_QUERIES = ivf.GRAPH_MAX_QUERIES
 ENCODE_MAX_LEVELS = 8             # levels of one rq.rq_encode call: the matrix-core encoder's envelope
 ENCODE_CHUNK = 1 << 17            # rows whose residuals exist at a time during the build
+
+
+MAX_BEAM = 16                     # beams of one step call: a parent is a byte, a lane per kept slot
+
+
+def env_beam(name):
+    """The beam width an environment variable asks for: unset = 1 (greedy); anything but an integer in 1..MAX_BEAM is a ValueError."""
+    raw = os.environ.get(name, "1")
+    if not re.fullmatch(r"\s*\d+\s*", raw) or not 1 <= int(raw) <= MAX_BEAM:
+        raise ValueError(f"{name}={raw!r} must be an integer in 1..{MAX_BEAM}")
+    return int(raw)
+
+
+def check_beam(beam, name="beam"):
+    if isinstance(beam, bool) or not isinstance(beam, int) or not 1 <= beam <= MAX_BEAM:
+        raise ValueError(f"{name}={beam!r} must be an integer in 1..{MAX_BEAM}")
+    return beam
 
 
 def parse_factory(param):
@@ -94,6 +120,9 @@ def train_codebook(docs, list_of, centroids, M, nbits, seed=1234, stats=None):
     if centroids is not None:
         xs = xs - centroids[list_of[rows].long()]
     xs = xs.contiguous()
+    train_beam = env_beam("MEVI_RQINDEX_TRAIN_BEAM")
+    if train_beam > 1:
+        return train_codebook_beam(xs, M, K, int(seed), train_beam, stats)
     book, codes = rq.train_rq_codebook(xs, M, K, seed=int(seed), n_init=1, max_iter=RQ_NITER)
     book = book.contiguous()
     if stats is not None:
@@ -102,10 +131,115 @@ def train_codebook(docs, list_of, centroids, M, nbits, seed=1234, stats=None):
     return book
 
 
-def encode(docs, rows, list_of, centroids, codebook, chunk=ENCODE_CHUNK):
+def train_codebook_beam(xs, M, K, seed, beam, stats=None):
+    """faiss's default trainer (MEVI_RQINDEX_TRAIN_BEAM = beam > 1): level i's k-means (`rq.kmeans`, seed + i, as the greedy trainer)
+    runs on the residual rows of ALL beam entries of the sample, [n_s * B, dim]; one step call then hands the beams on.  `stats`:
+    'train_rows', 'input_mse', 'level_mse' (mean error of the best path after each level), 'train_beam', 'beam_mse' (after the last)."""
+    n, dim = xs.shape
+    cur, book, level_mse = xs.view(n, 1, dim), [], []
+    for level in range(M):
+        centers, _, _ = rq.kmeans(cur.reshape(-1, dim), K, seed=seed + level, n_init=1, max_iter=RQ_NITER)
+        centers = centers.contiguous()
+        book.append(centers)
+        _, _, err, cur = beam_step(cur, centers, beam, want_res=level != M - 1)
+        level_mse.append(float(err[:, 0].double().mean()))
+    if stats is not None:
+        stats.update(train_rows=int(n), input_mse=float((xs.double() ** 2).sum(1).mean()), level_mse=level_mse, train_beam=int(beam),
+                     beam_mse=level_mse[-1])
+    return torch.stack(book).contiguous()
+
+
+def beam_step_is_fused(n, dim, K, B, L):
+    """True when `beam_step` takes mevi_rq_errbeam_step_f32 (csrc/rq_errbeam.hip): not MEVI_RQINDEX_BEAM_STEP=steps and the shape is
+    inside the kernel's envelope (dim <= 4096, ...); otherwise the composition `beam_step_composed` runs."""
+    mode = os.environ.get("MEVI_RQINDEX_BEAM_STEP", "fused")
+    if mode not in ("fused", "steps"):
+        raise ValueError(f"MEVI_RQINDEX_BEAM_STEP={mode!r} must be 'fused' or 'steps'")
+    return mode == "fused" and dense.rq_errbeam_step_workspace_bytes(n, dim, K, B, L) > 0
+
+
+def beam_step(res_in, centroids, L, res_out=None, want_res=True, workspace=None):
+    """One level of the beam encoder: `dense.rq_errbeam_step`, or the composition that states the same contract."""
+    n, B, dim = res_in.shape
+    if beam_step_is_fused(n, dim, centroids.shape[0], B, L):
+        return dense.rq_errbeam_step(res_in, centroids, L, res_out=res_out, want_res=want_res, workspace=workspace)
+    return beam_step_composed(res_in, centroids, L, res_out=res_out, want_res=want_res)
+
+
+def beam_step_composed(res_in, centroids, L, res_out=None, want_res=True):
+    """`dense.rq_errbeam_step` as mevi_rq_neg_dist_f32 -> torch.sort of the packed (err bits, b * K + c) keys -> mevi_gather_sub_f32
+    (MEVI_RQINDEX_BEAM_STEP=steps; any dim % 4 == 0).  The same bits: err is the negated score (exact), +0 or above, so its bit
+    pattern orders it, and the flat index in the low word breaks ties."""
+    lib = hip.lib()
+    n, B, dim = res_in.shape
+    K = centroids.shape[0]
+    Lo, dev = min(int(L), B * K), res_in.device
+    if want_res and res_out is None:
+        res_out = torch.empty((n, Lo, dim), dtype=torch.float32, device=dev)
+    if n == 0:
+        empty = torch.empty((0, Lo), dtype=torch.uint8, device=dev)
+        return empty, empty.clone(), torch.empty((0, Lo), dtype=torch.float32, device=dev), res_out if want_res else None
+    neg = torch.empty((n * B, K), dtype=torch.float32, device=dev)
+    with hip.device_guard(dev):
+        hip.check(lib.mevi_rq_neg_dist_f32(hip.ptr(res_in), n * B, dim, hip.ptr(centroids), K, hip.ptr(neg), hip.stream_ptr()),
+                  "mevi_rq_neg_dist_f32")
+        keys = ((-neg).view(torch.int32).view(n, B * K).to(torch.int64) << 32) | torch.arange(B * K, device=dev)[None]
+        keys = torch.sort(keys, dim=1).values[:, :Lo]
+        flat = keys & 0xFFFFFFFF
+        parent, code = flat // K, flat % K
+        err = (keys >> 32).to(torch.int32).view(torch.float32)
+        if want_res:
+            src = (torch.arange(n, device=dev)[:, None] * B + parent).reshape(-1).contiguous()
+            hip.check(lib.mevi_gather_sub_f32(hip.ptr(res_in), hip.ptr(src), hip.ptr(centroids), hip.ptr(code.to(torch.int32).reshape(-1).contiguous()),
+                                              n * Lo, dim, hip.ptr(res_out), hip.stream_ptr()), "mevi_gather_sub_f32")
+    return parent.to(torch.uint8), code.to(torch.uint8), err.contiguous(), res_out if want_res else None
+
+
+def encode_walk(docs, rows, list_of, centroids, codebook, beam, chunk=ENCODE_CHUNK, stats=None):
+    """`encode` with a beam of `beam` >= 1 paths (1: the greedy codes, by the beam's own route): per chunk of chunk // beam rows the
+    residual row as `encode` forms it, M step calls over two ping-pong buffers [rows, beam, dim] that write the (parent, code) traces
+    u8 [M, rows, beam], one backtrack into the chunk's code rows.  `stats['code_mse']`: the mean over all rows of the kept path's
+    error (the last level's err[:, 0]), summed in float64."""
+    check_beam(beam)
+    M, K, dim = codebook.shape
+    n = docs.shape[0] if rows is None else rows.numel()
+    dev = docs.device
+    codes = torch.empty((n, M), dtype=torch.uint8, device=dev)
+    per = max(1, chunk // beam)
+    width, most = beam, min(per, max(n, 1))                      # slots of a trace row; rows of the largest chunk
+    bufs = [torch.empty(most * width * dim, dtype=torch.float32, device=dev) for _ in range(2 if M > 1 else 0)]
+    trace = torch.zeros((2, M * most * width), dtype=torch.uint8, device=dev)     # (slots past a level's Lo are never reached)
+    ws = torch.empty(max(1, dense.rq_errbeam_step_workspace_bytes(min(per, n), dim, K, beam, beam)), dtype=torch.uint8, device=dev)
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    for a in range(0, n, per):
+        x = docs[a:a + per] if rows is None else docs[rows[a:a + per]]
+        if centroids is not None:
+            sel = list_of[a:a + per] if rows is None else list_of[rows[a:a + per]]
+            x = x - centroids[sel.long()]                       # the f32 residual, one rounding per element
+        x = x.contiguous()
+        r = x.shape[0]
+        parents, kept = (t[:M * r * width].view(M, r, width) for t in trace)
+        cur, B = x.view(r, 1, dim), 1
+        for j in range(M):
+            Lo, last = min(beam, B * K), j == M - 1
+            out = None if last else bufs[j & 1][:r * Lo * dim].view(r, Lo, dim)
+            parent, code, err, cur = beam_step(cur, codebook[j], beam, res_out=out, want_res=not last, workspace=ws)
+            parents[j, :, :Lo], kept[j, :, :Lo] = parent, code
+            B = Lo
+        total += err[:, 0].double().sum()
+        dense.rq_errbeam_codes(parents, kept, r, out=codes[a:a + per])
+    if stats is not None:
+        stats["code_mse"] = float(total) / max(1, n)
+    return codes
+
+
+def encode(docs, rows, list_of, centroids, codebook, chunk=ENCODE_CHUNK, beam=1, stats=None):
     """u8 [len(rows), M]: the codes of docs[rows] in that order (rows None: of all rows, in place), residuals and codes produced
     `chunk` rows at a time (never a second f32 copy of the corpus).  The M levels go through `rq.rq_encode` in groups of at most
-    ENCODE_MAX_LEVELS; between two groups the chunk's residual is taken on by one mevi_rq_residual_f32, in place."""
+    ENCODE_MAX_LEVELS; between two groups the chunk's residual is taken on by one mevi_rq_residual_f32, in place.
+    beam > 1: `encode_walk` (chunk // beam rows at a time); `stats` then receives 'code_mse'."""
+    if check_beam(beam) > 1:
+        return encode_walk(docs, rows, list_of, centroids, codebook, beam, chunk=chunk, stats=stats)
     M = codebook.shape[0]
     n = docs.shape[0] if rows is None else rows.numel()
     codes = torch.empty((n, M), dtype=torch.uint8, device=docs.device)
@@ -128,7 +262,8 @@ def encode(docs, rows, list_of, centroids, codebook, chunk=ENCODE_CHUNK):
 class RQIndex:
     """`index.train(doc); index.add(doc)` of 'IVF<n>,RQ<M>x<b>' (nlist=None: 'RQ<M>x<b>'): centroids, codebook, codes list by list."""
 
-    def __init__(self, docs, nlist, M, nbits, centroids=None, codebook=None, seed=1234):
+    def __init__(self, docs, nlist, M, nbits, centroids=None, codebook=None, seed=1234, beam=None):
+        self.beam = env_beam("MEVI_RQINDEX_BEAM") if beam is None else check_beam(beam)   # paths the encoder keeps (faiss: 5)
         assert docs.is_cuda and docs.dtype == torch.float32 and docs.dim() == 2
         nd, dim = docs.shape
         assert 1 <= nbits <= 8 and M >= 1, (M, nbits)
@@ -150,7 +285,9 @@ class RQIndex:
         self.codebook = (train_codebook(docs, self.list_of, self.centroids, M, nbits, seed, self.train_stats) if codebook is None
                          else codebook.to(dev).contiguous())
         assert self.codebook.shape == (M, self.K, dim), (self.codebook.shape, M, self.K, dim)
-        self.codes = encode(docs, None if nlist is None else self.ids, self.list_of, self.centroids, self.codebook)
+        self.encode_stats = {"beam": self.beam}                 # + 'code_mse' under a beam
+        self.codes = encode(docs, None if nlist is None else self.ids, self.list_of, self.centroids, self.codebook, beam=self.beam,
+                            stats=self.encode_stats)
 
     @property
     def n_lists(self):
@@ -244,7 +381,8 @@ def search(query, docs, k, nlist, M, nbits, nprobe=None, report=True):
         rec = {c: v / max(1, query.shape[0]) for c, v in rec.items()}
         sizes = (index.offsets[1:] - index.offsets[:-1])
         st = index.train_stats
-        print(f"[mevi_amd] {factory_name(nlist, M, nbits)} nprobe={index.clamp_nprobe(nprobe)}: recall vs exact search " +
+        beam = f" beam={index.beam}" if index.beam > 1 else ""    # (the greedy default prints the line it always printed)
+        print(f"[mevi_amd] {factory_name(nlist, M, nbits)} nprobe={index.clamp_nprobe(nprobe)}{beam}: recall vs exact search " +
               ", ".join(f"@{c} {v:.4f}" for c, v in rec.items()) +
               f"; {index.codes.numel()} bytes of codes; lists: min {int(sizes.min())} / mean {float(sizes.float().mean()):.0f} / "
               f"max {int(sizes.max())} documents; training error per level (mean squared residual norm of {st['train_rows']} rows, "

@@ -822,6 +822,16 @@ typedef struct mevi_ip_topk_stats {
  * workgroup label `label` (blockIdx & 7) takes, in ticket order, for n_dpairs x n_qtiles items.  Writes them when both arrays are
  * non-null; returns how many there are, -1 on bad arguments. */
 int64_t mevi_ip_filter_tile_walk(int64_t n_dpairs, int64_t n_qtiles, int label, int32_t *dpair, int32_t *qtile);
+/* Stealing in that walk (host arithmetic; the functions the kernel calls): a workgroup of `label` that has left `hop` labels
+ * behind (0: none, it draws from its own label's counter; 1 .. 7) draws from the counter of label *victim = (label + hop) & 7,
+ * and `ticket` of that counter is item *sweep_index of the n_items items in sweep order (P workgroups per label; tickets follow
+ * the 2 P static items of the victim's range).  Returns 1, or 0 with *sweep_index = -1 when the ticket lies past the victim's
+ * range (the workgroup moves on to hop + 1, and leaves after hop 7); -1 on bad arguments. */
+int mevi_ip_filter_steal_item(int64_t n_items, int P, int label, int hop, uint32_t ticket, int32_t *victim, int32_t *sweep_index);
+/* Tiles the ticketed walk computed in the calling thread's last search on the current device, and how many of them a workgroup
+ * drew from another label's counter (MEVI_IP_STEAL=0: none; =force: every ticketed one).  Call when the search has completed
+ * (reads the device).  Status. */
+int mevi_ip_topk_get_walk_counts(int64_t *tiles, int64_t *stolen);
 /* The launch schedule of the f16-image pass of mevi_ip_topk_indexed_f32 (host arithmetic, no device work; the function the pass
  * itself calls): nq queries, nd rows, lists of kprime keys with a candidate area of cap slots, design effect `dispersion` of the
  * row order (1: exchangeable).  Per launch: its rows, the rank of the kept list whose key is the launch's predicted threshold

@@ -480,11 +480,18 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_kernel(
   emit_tile<NI>(acc, tq, qrow0 + 32 * NI * wn, drow0 + 64 * wm, doc_end, buf, count, S, k, cap, id_base);
 }
 
+// Tiles and stolen tiles (drawn from another label's counter) of ip_filter_h16_kernel's launches of one search, a pair per
+// launch (the launches past the last slot share it): zeroed by the search's first init_state_kernel, added to once per workgroup,
+// read by mevi_ip_topk_get_walk_counts.
+constexpr int WALK_COUNT_SLOTS = 32;
+__device__ unsigned long long g_walk_counts[2 * WALK_COUNT_SLOTS];
+
 __global__ __launch_bounds__(256) void init_state_kernel(unsigned long long *buf, unsigned int *count,
                                                         float *tau, unsigned int *failed, long long nq,
-                                                        int S, int k, unsigned int *tickets, int n_tickets) {
+                                                        int S, int k, unsigned int *tickets, int n_tickets, int zero_walk_counts) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_tickets) tickets[i] = 0u;
+  if (zero_walk_counts && i < 2 * WALK_COUNT_SLOTS) g_walk_counts[i] = 0ull;
   const long long total = nq * (long long)k;
   if (i < total) {
     const long long q = i / k;
@@ -1197,8 +1204,15 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
     const float *__restrict__ Qh, int nq, const float *__restrict__ Dh, long long doc_begin, long long doc_end,
     int dimp, const float *__restrict__ tau, unsigned long long *__restrict__ buf,
     unsigned int *__restrict__ count, int S, int k, int cap, unsigned int id_base, int n_qtiles, int n_dpairs,
-    int flush_mask, unsigned int *__restrict__ tickets, unsigned int *__restrict__ tickets_next) {
+    int flush_mask, unsigned int *__restrict__ tickets, unsigned int *__restrict__ tickets_next, int steal, int count_slot
+#ifdef MEVI_IP_WALK_STAMPS   // diagnostic build only (profiles/r08_filter_steal.txt): never defined for the shipped library
+    , unsigned long long *__restrict__ stamps
+#endif
+    ) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+#ifdef MEVI_IP_WALK_STAMPS
+  const unsigned long long stamp_t0 = __builtin_amdgcn_s_memrealtime();
+#endif
   // Ticketed walk (walk_range / sweep_order, mfma_pp.h): label g = blockIdx & 7 owns items [range_base, range_base + range_len)
   // of the sweep order; its P workgroups take tickets 0 .. 2P-1 statically (their first two tiles), every later one from the
   // label's counter tickets[g], so the tiles in flight on an XCD stay ~P consecutive items however the workgroups drift.  Every
@@ -1214,14 +1228,35 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
   // of a tile that runs (`live`: the next tile exists), so its register is never reused while the atomic is in flight.
   // A ticket taken for a call that never comes is larger than one already found past the range: unused tickets are never
   // valid ones.
+  //
+  // Stealing (steal != 0; steal_victim / steal_item, mfma_pp.h).  Nothing balances the eight ranges against each other, and they
+  // end up to 3 % apart (profiles/r08_filter_steal.txt), so a workgroup that finds its label's ticket past the range becomes a
+  // thief: it draws from the counters of the labels (g + 1) & 7, (g + 2) & 7, ... with the same returning atomic -- ticket t of
+  // tickets[v] is item 2P + t of v's range whoever draws it, so the counters stay the only source and every item is still handed
+  // out exactly once, in sweep order inside v's range -- moves on when a ticket lies past v's range and leaves after the seventh
+  // label.  A change of label is synchronous: lane 0 waits for its atomic, hands the ticket to the other waves through a second
+  // LDS word (two, alternating per hop) behind a workgroup barrier, and issues the ticket of the call after next from the new
+  // counter; the one in flight from the old counter is past that range and is dropped.  At most seven such round trips per
+  // workgroup and launch; the steady tile-to-tile path is the one above.  A launch none of whose ranges exceeds 2P has no
+  // ticketed item and nobody steals.  A thief only touches this launch's set of counters, so the alternation of the two sets
+  // holds as before.  With stealing the atomics carry device scope (sc1): a label's counter is then drawn from several XCDs,
+  // whose L2s are not coherent.  steal == 2 (MEVI_IP_STEAL=force, tests): a workgroup starts at hop 1 and never draws from its
+  // own label's counter, so every ticketed item is computed by a workgroup of another label.  steal == 0: the walk without it.
+  // Every workgroup adds its tiles and those it drew from another label's counter to the launch's pair of g_walk_counts once, at its exit.
   const int g8 = blockIdx.x & 7, P = gridDim.x >> 3, j0 = blockIdx.x >> 3;
+  const int n_items = n_qtiles * n_dpairs;
   int range_base, range_len;
-  walk_range(n_qtiles * n_dpairs, g8, range_base, range_len);
+  walk_range(n_items, g8, range_base, range_len);
   if (j0 == 0 && threadIdx.x == 0) tickets_next[g8] = 0u;
-  unsigned int *const ctr = tickets + g8;
+  const bool thieving = steal != 0 && ((n_items + 7) >> 3) > 2 * P;   // the longest range has ticketed items
+  int hop = steal == 2 ? 1 : 0;       // the tickets come from label steal_victim(g8, hop)
+  int n_stolen = 0;
+  unsigned int *ctr = tickets + steal_victim(g8, hop);
+  TicketRange src = ticket_range(n_items, P, steal_victim(g8, hop));   // what a ticket of that counter means
   const unsigned int one = 1u;
   auto take_ticket = [&](unsigned int &v) {
-    asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(v) : "v"(ctr), "v"(one) : "memory");
+    if (steal) asm volatile("global_atomic_add %0, %1, %2, off sc0 sc1" : "=v"(v) : "v"(ctr), "v"(one) : "memory");
+    else asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(v) : "v"(ctr), "v"(one) : "memory");
   };
   unsigned int *const tk_word = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(lds) + h1_lds_bytes() + 8 * STASH_BYTES_PER_WAVE);
   int calls = 0;
@@ -1236,12 +1271,35 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
   int head_d = 0, head_q = 0, tail_d = 0, tail_q = 0, n_pend = 0;
 
   auto next = [&](H1Src &s) -> bool {
-    const int item = calls < 2 ? j0 + calls * P : 2 * P + (int)__builtin_amdgcn_readfirstlane(*tk_word);
+    int sweep = 0;   // the item's index in the sweep order
+    if (calls < 2) {
+      const int item = j0 + calls * P;
+      live = item < range_len;
+      sweep = range_base + item;
+    } else {
+      unsigned int ticket = (unsigned int)__builtin_amdgcn_readfirstlane(*tk_word);
+      live = steal_item(src, ticket, sweep);
+      while (!live && thieving && hop < 7) {   // on to the next label (uniform: every wave read the same ticket)
+        ++hop;
+        ctr = tickets + steal_victim(g8, hop);
+        src = ticket_range(n_items, P, steal_victim(g8, hop));
+        unsigned int *const hw = tk_word + 1 + (hop & 1);
+        if (t == 0) {
+          unsigned int now;
+          asm volatile("global_atomic_add %0, %1, %2, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(now) : "v"(ctr), "v"(one) : "memory");
+          *hw = now;
+        }
+        __syncthreads();
+        ticket = (unsigned int)__builtin_amdgcn_readfirstlane(*hw);
+        live = steal_item(src, ticket, sweep);
+        if (live && t == 0) take_ticket(tk);  // for the call after this one, from the new counter
+      }
+      if (live && hop) ++n_stolen;
+    }
     ++calls;
-    live = item < range_len;
     if (!live) return false;
     int dpair, qtile;
-    sweep_order(range_base + item, n_dpairs, n_qtiles, dpair, qtile);
+    sweep_order(sweep, n_dpairs, n_qtiles, dpair, qtile);
     if (n_pend == 0) head_d = dpair, head_q = qtile;
     else tail_d = dpair, tail_q = qtile;
     ++n_pend;
@@ -1286,7 +1344,20 @@ __global__ __launch_bounds__(PP_THREADS, 2) void ip_filter_h16_kernel(
     emit_tile16<NI>(acc, tq, qb, drow0 + 64 * wm, doc_end, tau, buf, count, S, k, cap, id_base, stash, (tiles_done & flush_mask) == 0);
   };
   h16_tile_stream<NI>(64, dimp / 32, lds, next, begin, emit, early, H1BlockedUnits());
+#ifdef MEVI_IP_WALK_STAMPS
+  const unsigned long long stamp_t1 = __builtin_amdgcn_s_memrealtime();
+#endif
   rec_flush(stash, tau, buf, count, S, k, cap);
+  if (t == 0) {
+    atomicAdd(&g_walk_counts[2 * count_slot], (unsigned long long)tiles_done);
+    if (n_stolen) atomicAdd(&g_walk_counts[2 * count_slot + 1], (unsigned long long)n_stolen);
+  }
+#ifdef MEVI_IP_WALK_STAMPS   // start, end of the tile loop, exit (100 MHz ticks) and tiles of this workgroup; nothing reads them but the host's dump
+  if (t == 0) {
+    unsigned long long *o = stamps + (size_t)blockIdx.x * 4;
+    o[0] = stamp_t0, o[1] = stamp_t1, o[2] = __builtin_amdgcn_s_memrealtime(), o[3] = (unsigned long long)tiles_done;
+  }
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -1971,9 +2042,69 @@ static QuerySide carve_query_side(Carver &c, int64_t nq, size_t image_bytes) {
 
 thread_local double g_growth = 0.0;
 thread_local int g_profile = 0;
+thread_local bool g_walk_zero = false;   // the next init_state_kernel zeroes g_walk_counts (the first pass of a search)
+thread_local int g_walk_launches = 0;    // ip_filter_h16_kernel launches of this search: their slots in g_walk_counts
+
+// MEVI_IP_STEAL: 0 = the ticketed walk without stealing (A/B; same lists), force = no workgroup draws from its own label's
+// counter (tests: every ticketed item is stolen), anything else or unset = stealing (ip_filter_h16_kernel)
+static int steal_mode() {
+  static const int m = [] { const char *e = getenv("MEVI_IP_STEAL"); return !e ? 1 : strcmp(e, "force") == 0 ? 2 : strcmp(e, "0") == 0 ? 0 : 1; }();
+  return m;
+}
 thread_local mevi_ip_topk_stats g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0.0};
 thread_local std::vector<hipEvent_t> g_events;  // triples: before filter, after filter, after compact
 thread_local std::vector<long long> g_chunk_rows;  // rows of the launch each triple brackets (profiling on)
+
+#ifdef MEVI_IP_WALK_STAMPS
+// Diagnostic build: ip_filter_h16_kernel's workgroups stamp their start, the end of their tile loop and their exit (four words
+// each) into slot `launch` of a buffer nothing else reads; profile_collect prints, per launch, when each label's workgroups
+// finished.  The shipped library has none of this (profiles/r08_filter_steal.txt).
+constexpr int STAMP_LAUNCHES = 32, STAMP_WGS = 2048;
+thread_local unsigned long long *g_stamps = nullptr;
+thread_local std::vector<unsigned> g_stamp_grids;
+static unsigned long long *stamp_slot(unsigned grid) {
+  if (!g_stamps && hipMalloc(&g_stamps, (size_t)STAMP_LAUNCHES * STAMP_WGS * 32) != hipSuccess) g_stamps = nullptr;
+  if (!g_stamps || grid > (unsigned)STAMP_WGS) return nullptr;
+  const size_t slot = g_stamp_grids.size() % STAMP_LAUNCHES;
+  g_stamp_grids.push_back(grid);
+  return g_stamps + slot * STAMP_WGS * 4;
+}
+static void stamps_dump() {
+  std::vector<unsigned long long> h((size_t)STAMP_WGS * 4);
+  for (size_t l = 0; getenv("MEVI_IP_TOPK_TRACE") && l < g_stamp_grids.size() && l < (size_t)STAMP_LAUNCHES; ++l) {
+    const unsigned grid = g_stamp_grids[l];
+    if (hipMemcpy(h.data(), g_stamps + l * STAMP_WGS * 4, (size_t)grid * 32, hipMemcpyDeviceToHost) != hipSuccess) break;
+    unsigned long long t0 = ~0ull, s_last = 0, tiles = 0;
+    for (unsigned w = 0; w < grid; ++w) {
+      if (h[4 * w] < t0) t0 = h[4 * w];
+      if (h[4 * w] > s_last) s_last = h[4 * w];
+      tiles += h[4 * w + 3];
+    }
+    const auto us = [&](unsigned long long v) { return (double)(v - t0) * 0.01; };
+    double lo = 1e30, hi = 0.0;
+    fprintf(stderr, "ip_topk stamps launch %zu: grid %u  tiles %llu  last start %.2f us\n", l, grid, tiles, us(s_last));
+    for (int g = 0; g < 8; ++g) {
+      unsigned long long loop_first = ~0ull, loop_last = 0, exit_first = ~0ull, exit_last = 0, tg = 0, tmin = ~0ull, tmax = 0;
+      for (unsigned w = (unsigned)g; w < grid; w += 8) {
+        const unsigned long long *o = &h[4 * w];
+        if (o[1] < loop_first) loop_first = o[1];
+        if (o[1] > loop_last) loop_last = o[1];
+        if (o[2] < exit_first) exit_first = o[2];
+        if (o[2] > exit_last) exit_last = o[2];
+        tg += o[3];
+        if (o[3] < tmin) tmin = o[3];
+        if (o[3] > tmax) tmax = o[3];
+      }
+      fprintf(stderr, "  label %d: tiles %llu (%llu..%llu per workgroup)  loop end %.2f .. %.2f us  exit %.2f .. %.2f us\n", g, tg, tmin,
+              tmax, us(loop_first), us(loop_last), us(exit_first), us(exit_last));
+      if (us(exit_last) < lo) lo = us(exit_last);
+      if (us(exit_last) > hi) hi = us(exit_last);
+    }
+    fprintf(stderr, "  labels' last exits: first %.2f us, last %.2f us, spread %.2f us\n", lo, hi, hi - lo);
+  }
+  g_stamp_grids.clear();
+}
+#endif
 
 static void profile_mark(hipStream_t stream) {
   if (!g_profile) return;
@@ -1994,7 +2125,16 @@ static void profile_collect() {
     if (getenv("MEVI_IP_TOPK_TRACE") && i / 3 < g_chunk_rows.size())  // per-launch breakdown on stderr
       fprintf(stderr, "ip_topk launch %zu: %lld rows  filter %.3f ms  compact %.3f ms\n", i / 3, g_chunk_rows[i / 3], f, c);
   }
+  if (getenv("MEVI_IP_TOPK_TRACE") && g_profile && g_walk_launches > 0) {  // tiles per launch of the ticketed walk, and those stolen
+    unsigned long long c[2 * WALK_COUNT_SLOTS];
+    if (hipMemcpyFromSymbol(c, HIP_SYMBOL(g_walk_counts), sizeof(c)) == hipSuccess)
+      for (int l = 0; l < g_walk_launches && l < WALK_COUNT_SLOTS; ++l)
+        fprintf(stderr, "ip_topk walk launch %d: %llu tiles, %llu stolen\n", l, c[2 * l], c[2 * l + 1]);
+  }
   g_chunk_rows.clear();
+#ifdef MEVI_IP_WALK_STAMPS
+  stamps_dump();
+#endif
   for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
   g_events.clear();
 }
@@ -2270,7 +2410,8 @@ static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
   const long long init_n = total > nq ? total : nq;
   const int n_tickets = TICKET_SLOTS * 8;
   hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)(((init_n > n_tickets ? init_n : n_tickets) + 255) / 256)), dim3(256), 0, stream,
-                     st.buf, st.count, st.tau, st.failed, (long long)nq, g.S, g.k, st.tickets, n_tickets);
+                     st.buf, st.count, st.tau, st.failed, (long long)nq, g.S, g.k, st.tickets, n_tickets, g_walk_zero ? 1 : 0);
+  g_walk_zero = false;
   const size_t compact_lds = (size_t)g.S * 8 + 2048;  // keys + histogram
   if (compact_lds > 65536) {  // dynamic LDS beyond 64 KiB must be opted into
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(compact_kernel),
@@ -2355,12 +2496,16 @@ static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
       long long d0 = (long long)seen, d1 = (long long)(seen + chunk);
       const float *tau_c = st.tau;
       // the thirteen arguments every filter kernel starts with, then its own
-      void *args[18] = {(void *)&a.Q, &nq_i, (void *)&a.D, &d0, &d1, (void *)&a.dim, (void *)&tau_c, (void *)&st.buf,
+      void *args[21] = {(void *)&a.Q, &nq_i, (void *)&a.D, &d0, &d1, (void *)&a.dim, (void *)&tau_c, (void *)&st.buf,
                         (void *)&st.count, (void *)&g.S, (void *)&g.k, (void *)&g.cap, (void *)&a.id_base};
       unsigned grid = (unsigned)nwg;
       int flush_mask = H16_FLUSH_EVERY - 1;
       // this launch's eight ticket counters (zero: init_state_kernel, or the launch before) and the next launch's, which it zeroes
       unsigned int *tickets = st.tickets + 8 * (launches & 1), *tickets_next = st.tickets + 8 * ((launches + 1) & 1);
+      int steal = 0, count_slot = 0;
+#ifdef MEVI_IP_WALK_STAMPS
+      unsigned long long *stamp_ptr = nullptr;
+#endif
       if (f.grid == FilterGrid::SmallStream) {
         const int64_t nb = (chunk + 255) / 256;
         grid = (unsigned)(nb < n_cu ? nb : n_cu);
@@ -2386,6 +2531,19 @@ static int64_t run_pass(const PassArgs &a, hipStream_t stream) {
         args[15] = &flush_mask;
         args[16] = (void *)&tickets;
         args[17] = (void *)&tickets_next;
+        steal = steal_mode();
+        count_slot = g_walk_launches < WALK_COUNT_SLOTS ? g_walk_launches : WALK_COUNT_SLOTS - 1;
+        ++g_walk_launches;
+        args[18] = &steal;
+        args[19] = &count_slot;
+#ifdef MEVI_IP_WALK_STAMPS
+        stamp_ptr = stamp_slot(grid);
+        if (!stamp_ptr) {
+          set_error("ip_topk: no stamp buffer for a grid of %u", grid);
+          return -1;
+        }
+        args[20] = (void *)&stamp_ptr;
+#endif
       }
       if (hipLaunchKernel(f.fn, dim3(grid), dim3(PP_THREADS), args, f.lds, stream) != hipSuccess) {
         set_error("ip_topk: filter kernel launch failed");
@@ -2456,6 +2614,8 @@ static void begin_call() {
   g_stats = {0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0.0};
   for (hipEvent_t e : g_events) (void)hipEventDestroy(e);
   g_events.clear();
+  g_walk_zero = true;
+  g_walk_launches = 0;
 }
 
 // Shape, pointer, alignment, id-range and workspace checks of a search, in the order and with the codes the entry points have
@@ -2519,6 +2679,26 @@ extern "C" int64_t mevi_ip_filter_tile_walk(int64_t n_dpairs, int64_t n_qtiles, 
     qtile[t] = b;
   }
   return len;
+}
+
+extern "C" int mevi_ip_filter_steal_item(int64_t n_items, int P, int label, int hop, uint32_t ticket, int32_t *victim, int32_t *sweep_index) {
+  if (n_items <= 0 || n_items > 0x7fffffffLL || P <= 0 || P > (1 << 20) || label < 0 || label > 7 || hop < 0 || hop > 7) return -1;
+  const int v = steal_victim(label, hop);
+  int sweep = -1;
+  const bool ok = steal_item(ticket_range((int)n_items, P, v), ticket, sweep);
+  if (victim) *victim = v;
+  if (sweep_index) *sweep_index = ok ? sweep : -1;
+  return ok ? 1 : 0;
+}
+
+extern "C" int mevi_ip_topk_get_walk_counts(int64_t *tiles, int64_t *stolen) {
+  unsigned long long c[2 * WALK_COUNT_SLOTS];
+  MEVI_HIP_CHECK(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_walk_counts), sizeof(c)));
+  unsigned long long a = 0, b = 0;
+  for (int l = 0; l < g_walk_launches && l < WALK_COUNT_SLOTS; ++l) a += c[2 * l], b += c[2 * l + 1];
+  if (tiles) *tiles = (int64_t)a;
+  if (stolen) *stolen = (int64_t)b;
+  return MEVI_OK;
 }
 
 extern "C" int64_t mevi_ip_topk_plan(int64_t nq, int64_t nd, int64_t kprime, int64_t cap, double dispersion, int64_t max_launches,

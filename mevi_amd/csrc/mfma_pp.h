@@ -94,6 +94,28 @@ __host__ __device__ inline void sweep_order(int t, int n_a, int n_b, int &a_tile
   b_tile = b0 + (r - a_in * w);
 }
 
+// Stealing in the ticketed walk: a workgroup of label g whose own counter has run past its range draws from the counters of the
+// labels (g + 1) & 7, (g + 2) & 7, ... (steal_victim, hop = 1 .. 7) and leaves after the seventh.  A ticket t of label v's
+// counter, whoever drew it, is item 2 P + t of v's range (tickets 0 .. 2 P - 1 are the static first two tiles of v's own P
+// workgroups): steal_item gives its index in the sweep order, false when the ticket lies past the range (ticket_range: the
+// range's ticketed part, which the kernel keeps in two scalars between changes of label).  Host and device share them
+// (mevi_ip_filter_steal_item exposes them to tests/test_steal_order_cpu.py).
+__host__ __device__ inline int steal_victim(int g, int hop) { return (g + hop) & 7; }
+struct TicketRange {
+  int first;            // sweep index of ticket 0: the item behind the 2 P static ones
+  unsigned int count;   // ticketed items of the range
+};
+__host__ __device__ inline TicketRange ticket_range(int n_items, int P, int v) {
+  int lo, len;
+  walk_range(n_items, v, lo, len);
+  return {lo + 2 * P, len > 2 * P ? (unsigned int)(len - 2 * P) : 0u};
+}
+__host__ __device__ inline bool steal_item(const TicketRange &r, unsigned int ticket, int &sweep_index) {
+  if (ticket >= r.count) return false;
+  sweep_index = r.first + (int)ticket;
+  return true;
+}
+
 // aptr[i]: this thread's staging pointers into its group's A tile (row srow+32i, + skq),
 // bptr[i]: into the shared B tile (row (QT/2)*grp + srow + 32i, + skq); rows pre-clamped.
 // acc[mi][ni]: 32x32 accumulators of wave (wm, wn): A rows 64*wm + 32*mi + ..., B rows

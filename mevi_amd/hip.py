@@ -180,6 +180,9 @@ _SIGNATURES = {
                                        c_void_p]),
     "mevi_first_hits_i64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "mevi_ip_filter_tile_walk": (c_int64, [c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "mevi_ip_filter_steal_item": (c_int, [c_int64, c_int, c_int, c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.POINTER(ctypes.c_int32)]),
+    "mevi_ip_topk_get_walk_counts": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "mevi_ip_topk_set_growth": (None, [c_double]),
     "mevi_ip_topk_set_profiling": (None, [c_int]),
     "mevi_ip_topk_plan": (c_int64, [c_int64, c_int64, c_int64, c_int64, c_double, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -355,6 +358,14 @@ def check(status, what):
     if status != 0:
         msg = lib().mevi_last_error().decode("utf-8", "replace")
         raise MeviHipError(f"{what} failed with status {status}: {msg}")
+
+
+def ip_walk_counts():
+    """(tiles, stolen) of the ticketed filter walk in this thread's last dense search on the current device
+    (mevi_ip_topk_get_walk_counts); call once the search has completed."""
+    tiles, stolen = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().mevi_ip_topk_get_walk_counts(ctypes.byref(tiles), ctypes.byref(stolen)), "mevi_ip_topk_get_walk_counts")
+    return tiles.value, stolen.value
 
 
 def require_gpu():
